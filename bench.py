@@ -8,12 +8,15 @@ One "step" = one pass of the hot path over one batch of synthetic frames residen
 Workload at N=1 (BASELINE.json configs[1]): uniform synthetic cloud, 116 000 points/frame ->
 ~90 k non-empty voxels, 1 frame per GPU; frames shard data-parallel across ranks (weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 with two extra objects:
   roofline      dominant kernel group = the SRA attention core forward (sra_fwd_mfma_k<NT> launch group):
                 achieved = 2056 B/token x tokens / mean HIP-event duration of the group over the timed region,
                 vs the 8 TB/s HBM peak.
-  cpu_baseline  the CPU port of the reference path (oracle/cpu_pipeline.py) timed on the host cores for one
+  cpu_baseline  (--full) the CPU port of the reference path (oracle/cpu_pipeline.py) timed on the host cores for one
                 frame of the same workload, fwd+bwd (rank 0, N=1 only).
+A plain run sets up, warms up, times --steps steps and prints the line; --full adds every leg beside the headline
+(other precisions, clouds and workloads, parity against the CPU port, host time, rooflines that take runs of their own).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -166,6 +169,33 @@ GC_WATCH = None
 def note(msg):
     """progress marker on stderr (the line itself goes to stdout): which leg a run was in when something went wrong"""
     print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: `arrays` (name -> tensor, in the order given) as out_dir/<name>.npy, float64 kept, everything else as
+    float32.  If they do not fit in `budget` bytes together, each array larger than an even share of it is replaced by a fixed
+    sample of the rows of its 2-D view [-1, last dimension] (numpy seed 0, sorted row indices, the same for every run with the
+    same sizes) and out_dir/<name>_rows.npy holds the indices of the rows kept (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    share = budget // (2 * max(1, len(host)))      # leaves room for the row index files
+    for name, a in host.items():
+        if total > budget and a.nbytes > share:
+            a = a.reshape(-1, a.shape[-1]) if a.ndim >= 2 else a.reshape(-1)
+            keep = max(1, min(a.shape[0], share // max(1, a.nbytes // a.shape[0])))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(out_dir, name + '_rows.npy'), rows.astype(np.float64))
+            a = np.ascontiguousarray(a[rows])
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    note(f'outputs of the last timed step written to {out_dir}: ' + ', '.join(sorted(host)))
 
 
 class StepTimes(object):
@@ -655,6 +685,15 @@ def parse_args():
     ap.add_argument('--no-voxelize-roofline', action='store_true', help='skip the dynamic-voxelize microbenchmark')
     ap.add_argument('--no-gemm-tuning', action='store_true',
                     help='do not let PyTorch TunableOp pick the hipBLASLt/rocBLAS solution of each dense GEMM shape')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: the side legs (forward only, config as is, bf16, LiDAR-like '
+                         'cloud, matmul modes, standard attention), cpu_baseline + parity, host time per step, the collective '
+                         'costs, the voxelize roofline, the live traffic passes and the compact legs of the other workloads.  '
+                         'Without it a run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (output features, voxel coordinates, '
+                         'parameter gradients) as DIR/<name>.npy in float32, at most 64 MB in all (rank 0); bench_outputs/ is '
+                         'git-ignored')
     return ap.parse_args()
 
 
@@ -702,10 +741,11 @@ def workload_legs(args):
             ('fsd_bs2', 10, 3, 240, ('--workload', 'fsd', '--frames-per-gpu', '2', '--no-cpu-baseline')), ('fsdv2', 10, 3, 300, ()))
     for name, steps, warm, limit, extra in plan:
         note(f'leg: workload {name} (own process)')
-        cmd = [sys.executable, os.path.abspath(__file__), '--workload', name, '--compact', '--steps', str(steps), '--warmup',
-               str(warm)]
+        cmd = [sys.executable, os.path.abspath(__file__), '--workload', name, '--compact', '--full', '--steps', str(steps),
+               '--warmup', str(warm)]
         if extra:
-            cmd = [sys.executable, os.path.abspath(__file__), *extra, '--compact', '--steps', str(steps), '--warmup', str(warm)]
+            cmd = [sys.executable, os.path.abspath(__file__), *extra, '--compact', '--full', '--steps', str(steps), '--warmup',
+                   str(warm)]
         t0 = time.perf_counter()
         try:
             sub = subprocess.run(cmd, capture_output=True, text=True, timeout=limit, cwd=ROOT)
@@ -754,6 +794,11 @@ def _main(args, line_out):
         args.no_voxelize_roofline = True
         if args.workload not in ('fsd', 'fsdv2'):
             args.no_cpu_baseline = True
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the line - everything else is behind --full
+        args.no_lidar_leg = args.no_forward_only_leg = args.no_config_as_is_leg = args.no_traffic_remeasure = True
+        args.no_f32x3_leg = args.no_bf16_leg = args.no_bf16_own_process = args.no_std_attention_leg = True
+        args.no_workload_legs = args.no_voxelize_roofline = args.no_cpu_baseline = True
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # launched as plain `python bench.py --gpus N`: start one rank per GPU ourselves, the way the reference's
@@ -775,7 +820,8 @@ def _main(args, line_out):
 
     if args.workload in ('fsd', 'fsdv2'):
         import bench_workloads
-        bench_workloads.run(args, rank, world, dev, make_reducer, line_out=line_out, step_times_cls=StepTimes)
+        bench_workloads.run(args, rank, world, dev, make_reducer, line_out=line_out, step_times_cls=StepTimes,
+                            dump_fn=dump_outputs)
         if world > 1:
             dist.destroy_process_group()
         return
@@ -932,12 +978,22 @@ def _main(args, line_out):
     main_times = StepTimes()
     main_times.mark()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    last_out = None
+    for i in range(args.steps):
+        o = step()
+        if i == args.steps - 1:
+            last_out = o
+        del o
         main_times.mark()
     sync()
     elapsed = time.perf_counter() - t0
     main_times.close()
+    if args.dump_outputs and rank == 0:
+        grads = [p.grad.reshape(-1) for p in params if p.grad is not None]     # none with --fwd-only
+        dump_outputs(args.dump_outputs, dict(
+            [('voxel_feats' if last_out.dim() == 2 else 'bev_feats', last_out.detach()),
+             ('voxel_coors', model.last_voxel_coors)] + ([('param_grads', torch.cat(grads))] if grads else [])))
+    del last_out
     if os.environ.get('SST_BENCH_ALLOC_TRACE_TIMED'):
         snap = torch.cuda.memory._snapshot()
         for e in [e for tr in snap.get('device_traces', []) for e in tr if e.get('action') in ('segment_alloc', 'segment_free')][:20]:
@@ -980,8 +1036,8 @@ def _main(args, line_out):
         except Exception as e:
             print('snapshot failed:', e, file=sys.stderr)
 
-    comm = collective_costs(reducer, dev) if reducer is not None else None   # every rank takes part
-    main_host_ms = host_ms_per_step() if world == 1 else None                 # outside the timed region
+    comm = collective_costs(reducer, dev) if (reducer is not None and args.full) else None   # every rank takes part
+    main_host_ms = host_ms_per_step() if (world == 1 and args.full) else None                 # outside the timed region
 
     # Outside the timed region: the forward-only rate of the same workload (BASELINE.json configs[1] is quoted
     # forward-only, the metric forward + backward; `value` is the harder one, this is reported beside it).
@@ -1135,7 +1191,7 @@ def _main(args, line_out):
         if world == 1 and not args.no_bf16_own_process:
             note('leg: reduced precision, own process')
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), '--precision', 'bf16', '--steps', str(args.steps), '--warmup',
+            cmd = [sys.executable, os.path.abspath(__file__), '--full', '--precision', 'bf16', '--steps', str(args.steps), '--warmup',
                    str(max(3, args.warmup)), '--points', str(args.points), '--blocks', str(args.blocks), '--no-cpu-baseline',
                    '--no-lidar-leg', '--no-forward-only-leg', '--no-config-as-is-leg', '--no-traffic-remeasure', '--no-f32x3-leg',
                    '--no-time-sra-bwd', '--no-voxelize-roofline', '--no-workload-legs']

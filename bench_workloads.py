@@ -625,9 +625,11 @@ def _conv_precision_leg(mode, timed_mode, model, clouds, step, sync, args, world
             'max_err_vs_timed_mode_forward_rel_to_output_scale': errs}
 
 
-def run(args, rank, world, dev, make_reducer, line_out=None, step_times_cls=None):
+def run(args, rank, world, dev, make_reducer, line_out=None, step_times_cls=None, dump_fn=None):
     """bench.py's contract for --workload fsd | fsdv2: W warm-up steps, K timed steps between barriers, max over ranks,
-    one JSON line from rank 0 (to `line_out`: bench.py keeps everything else off its stdout)."""
+    one JSON line from rank 0 (to `line_out`: bench.py keeps everything else off its stdout).  The host time per step and the
+    instrumented roofline pass run with `args.full` only; with `args.dump_outputs`, `dump_fn(dir, arrays)` receives the loss
+    and the parameter gradients of the last timed step."""
     import sys
     line_out = line_out if line_out is not None else sys.stdout
     spec = WORKLOADS[args.workload]
@@ -674,6 +676,7 @@ def run(args, rank, world, dev, make_reducer, line_out=None, step_times_cls=None
         loss.backward()
         if reducer is not None:
             reducer.finish()        # parameters without a gradient this step (an empty stage) travel as zeros
+        return loss
 
     def sync():
         torch.cuda.synchronize()
@@ -691,16 +694,25 @@ def run(args, rank, world, dev, make_reducer, line_out=None, step_times_cls=None
     if times is not None:
         times.mark()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    last_loss = None
+    for i in range(args.steps):
+        loss = step()
+        if i == args.steps - 1:
+            last_loss = loss
+        del loss
         if times is not None:
             times.mark()
     sync()
     elapsed = time.perf_counter() - t0
     step_ms = times.close().stats() if times is not None else None
+    if getattr(args, 'dump_outputs', None) and rank == 0 and dump_fn is not None:
+        dump_fn(args.dump_outputs, {'loss': last_loss.detach().reshape(1),
+                                    'param_grads': torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None])})
+    del last_loss
+    full = getattr(args, 'full', True)
     # interpreter + launch time of a step: forward and backward timed on the host with the device idle at their start
     host_ms = None
-    if world == 1:
+    if world == 1 and full:
         tot = 0.0
         for _ in range(2):
             for p in params:
@@ -721,7 +733,7 @@ def run(args, rank, world, dev, make_reducer, line_out=None, step_times_cls=None
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    conv, seg = _conv_roofline(model, clouds)
+    conv, seg = _conv_roofline(model, clouds) if full else (None, None)
     x3 = mfma_leg = None
     if not getattr(args, 'no_f32x3_leg', False):
         x3 = _conv_precision_leg('f32x3', conv_prec, model, clouds, step, sync, args, world, dev)

@@ -1,12 +1,15 @@
-"""The drop-in contract at its entry: the reference's shipped config files, read from their text, construct through
-sst_amd's registries UNMODIFIED.  Build container only (the config text lives
-under /root/reference); construction is pure host work, no kernel runs.
+"""The drop-in contract at its entry: the reference's shipped config files construct through sst_amd's registries UNMODIFIED
+(VERDICT round 3 item 1).  Their resolved `model` dictionaries are stored under
+tests/golden/configs/<group>/ (tests/golden/make_config_fixtures.py), so the construction runs anywhere; where the reference's
+config text is present, test_construct_fixtures_are_the_shipped_configs checks that the stored dictionaries still equal it.
+Construction is pure host work, no kernel runs.
 
   configs/fsdv2/*.py          SingleStageFSDV2 / FSDV2 with multiscale_cfg (all five) and as_rpn (Waymo): BASELINE configs[4]
   configs/fsd/*.py            FSD with the sparse-convolution or the SST segmentor: BASELINE configs[3]
   configs/sst_refactor/*.py,  voxel_layer / voxel_encoder / middle_encoder / backbone of DynamicVoxelNet / DynamicCenterPoint:
   configs/sst/*.py            BASELINE configs[1..2]
 and bench_workloads.FSDV2_CFG (what `bench.py --workload fsdv2` runs) is compared number by number with fsdv2_nusc_1x.py."""
+import ast
 import copy
 import glob
 import os
@@ -15,7 +18,8 @@ import pytest
 import torch
 
 REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'configs')), reason='needs the reference tree')
+FIXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'configs')
+GROUPS = ('fsdv2', 'fsd', 'sst_refactor', 'sst')
 
 
 def _merge(base, new):
@@ -41,14 +45,44 @@ def load_config(path):
     return _merge(merged, cfg)
 
 
-def _configs(sub):
+def shipped_configs(sub):
+    """the reference's config files of one group (empty where the reference tree is absent)"""
     return sorted(p for p in glob.glob(os.path.join(REF, 'configs', sub, '*.py')) if 'do_not_use' not in p)
 
 
-@pytest.mark.parametrize('path', _configs('fsdv2'), ids=os.path.basename)
+def _fixtures(sub):
+    return sorted(glob.glob(os.path.join(FIXTURES, sub, '*.model.py')))
+
+
+def _config_id(path):
+    return os.path.basename(path)[:-len('.model.py')] + '.py'
+
+
+def load_model(path):
+    """the stored `model` dictionary of a shipped config (a Python literal: tuples and integer keys as in the config)"""
+    return ast.literal_eval(open(path).read())
+
+
+def test_every_group_has_fixtures():
+    for sub in GROUPS:
+        assert _fixtures(sub), sub
+
+
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'configs')), reason='needs the reference tree')
+def test_construct_fixtures_are_the_shipped_configs():
+    for sub in GROUPS:
+        shipped = shipped_configs(sub)
+        assert [os.path.basename(p) for p in shipped] == [_config_id(p) for p in _fixtures(sub)], sub
+        for path in shipped:
+            want = load_config(path)['model']
+            got = load_model(os.path.join(FIXTURES, sub, os.path.basename(path)[:-len('.py')] + '.model.py'))
+            assert got == want and repr(_plain(got)) == repr(_plain(want)), path
+
+
+@pytest.mark.parametrize('path', _fixtures('fsdv2'), ids=_config_id)
 def test_fsdv2_configs_construct(path):
     import sst_amd
-    model = load_config(path)['model']
+    model = load_model(path)
     det = sst_amd.build_detector(model)
     assert type(det).__name__ == model['type'] and isinstance(det, sst_amd.VirtualVoxelExtractor)
     keys = set(det.state_dict())
@@ -70,10 +104,10 @@ def test_fsdv2_configs_construct(path):
     assert list(ms['target_sparse_shape']) == list(model['backbone']['sparse_shape'])
 
 
-@pytest.mark.parametrize('path', _configs('fsd'), ids=os.path.basename)
+@pytest.mark.parametrize('path', _fixtures('fsd'), ids=_config_id)
 def test_fsd_configs_construct(path):
     import sst_amd
-    model = load_config(path)['model']
+    model = load_model(path)
     det = sst_amd.build_detector(model)
     assert type(det).__name__ == model['type']
     keys = set(det.state_dict())
@@ -88,11 +122,11 @@ def test_fsd_configs_construct(path):
         assert tuple(det.cluster_assigner.gpu_clustering) == tuple(model['cluster_assigner']['gpu_clustering'])
 
 
-@pytest.mark.parametrize('path', _configs('sst_refactor') + _configs('sst'), ids=os.path.basename)
+@pytest.mark.parametrize('path', _fixtures('sst_refactor') + _fixtures('sst'), ids=_config_id)
 def test_sst_configs_construct(path):
     """the four hot-path sub-configs of DynamicVoxelNet / DynamicCenterPoint (detectors/dynamic_voxelnet.py:38-71)"""
     import sst_amd
-    model = load_config(path)['model']
+    model = load_model(path)
     layer = sst_amd.Voxelization(**model['voxel_layer'])
     vfe = sst_amd.build_voxel_encoder(model['voxel_encoder'])
     mid = sst_amd.build_middle_encoder(model['middle_encoder'])
@@ -107,8 +141,8 @@ def test_sst_configs_construct(path):
 def test_bench_fsdv2_config_is_the_shipped_nuscenes_config():
     """`bench.py --workload fsdv2` (bench_workloads.FSDV2_CFG) against configs/fsdv2/fsdv2_nusc_1x.py, number by number"""
     import bench_workloads as BW
-    cfg = load_config(os.path.join(REF, 'configs/fsdv2/fsdv2_nusc_1x.py'))
-    model, seg, mine = cfg['model'], cfg['model']['segmentor'], BW.FSDV2_CFG
+    model = load_model(os.path.join(FIXTURES, 'fsdv2', 'fsdv2_nusc_1x.model.py'))
+    seg, mine = model['segmentor'], BW.FSDV2_CFG
     assert tuple(mine['seg_voxel']) == tuple(seg['voxel_layer']['voxel_size'])
     assert list(mine['pc_range']) == list(seg['voxel_layer']['point_cloud_range'])
     assert tuple(mine['virtual_voxel']) == tuple(model['voxel_encoder']['voxel_size'])

@@ -8,12 +8,12 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --workload fsd > $OUT/bench_workload_fsd.json 2> $OUT/bench_fsd.err
-python bench.py --workload fsdv2 > $OUT/bench_workload_fsdv2.json 2> $OUT/bench_fsdv2.err
-python bench.py --workload sst_bs2 --no-cpu-baseline > $OUT/bench_workload_sst_bs2.json 2> /dev/null
-python bench.py --workload sst_bev > $OUT/bench_workload_sst_bev.json 2> /dev/null
-python bench.py --cloud lidar --no-bf16-leg --no-f32x3-leg --no-forward-only-leg --no-traffic-remeasure > $OUT/bench_cloud_lidar.json 2> /dev/null
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --workload fsd > $OUT/bench_workload_fsd.json 2> $OUT/bench_fsd.err
+python bench.py --full --workload fsdv2 > $OUT/bench_workload_fsdv2.json 2> $OUT/bench_fsdv2.err
+python bench.py --full --workload sst_bs2 --no-cpu-baseline > $OUT/bench_workload_sst_bs2.json 2> /dev/null
+python bench.py --full --workload sst_bev > $OUT/bench_workload_sst_bev.json 2> /dev/null
+python bench.py --full --cloud lidar --no-bf16-leg --no-f32x3-leg --no-forward-only-leg --no-traffic-remeasure > $OUT/bench_cloud_lidar.json 2> /dev/null
 python tools/dense_x6_bench.py > $OUT/dense_f32_vs_f32x6_microbench.txt 2>&1
 python tools/conv_modes.py fsd > $OUT/conv_modes_fsd.txt 2>&1
 cd /tmp && export TMPDIR=/tmp

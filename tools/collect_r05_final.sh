@@ -7,10 +7,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --workload sst_center > $OUT/bench_workload_sst_center.json 2> $OUT/bench_center.err
-python bench.py --workload sst_bs2 --no-cpu-baseline > $OUT/bench_workload_sst_bs2.json 2> /dev/null
-python bench.py --cloud lidar --no-bf16-leg --no-f32x3-leg --no-forward-only-leg --no-traffic-remeasure > $OUT/bench_cloud_lidar.json 2> /dev/null
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --workload sst_center > $OUT/bench_workload_sst_center.json 2> $OUT/bench_center.err
+python bench.py --full --workload sst_bs2 --no-cpu-baseline > $OUT/bench_workload_sst_bs2.json 2> /dev/null
+python bench.py --full --cloud lidar --no-bf16-leg --no-f32x3-leg --no-forward-only-leg --no-traffic-remeasure > $OUT/bench_cloud_lidar.json 2> /dev/null
 python tools/step_segments.py 30 > $OUT/step_segments_uniform.json 2> /dev/null
 python tools/step_segments.py 30 0 lidar > $OUT/step_segments_lidar.json 2> /dev/null
 cd /tmp && export TMPDIR=/tmp
