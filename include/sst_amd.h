@@ -1122,6 +1122,62 @@ int sst_spconv_wgrad_f32(const float* d_x, int64_t ldx, const float* d_dy, int64
                          int64_t pair_ld, int64_t total_pairs, int x_side, const int32_t* d_num, int kvol, int cin,
                          int cout, float* d_dw, void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Rotated-box ops of the heads and the FSD training step (csrc/box_ops.hip).  fp32 only; deterministic (no atomics);
+ * everything on `stream`.  BEV boxes are [x1, y1, x2, y2, ry] (the reference's xywhr2xyxyr form), LiDAR boxes
+ * [x, y, z_bottom, w, l, h, rz].
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_BOX_OVERLAP 0   /* overlap area of the rotated boxes                                       */
+#define SST_BOX_IOU 1       /* rotated IoU, overlap / max(area_a + area_b - overlap, 1e-8)              */
+#define SST_BOX_IOU_AXIS 2  /* axis-aligned IoU, ry ignored (iou_normal)                                */
+#define SST_PIB_FIRST 0       /* points in boxes: smallest index of a box holding the point, else -1   */
+#define SST_PIB_MEMBERSHIP 1  /* points in boxes: 0 / 1 per (point, box)                               */
+
+/* Pairwise BEV overlap matrix.  Replaces iou3d_cuda.boxes_overlap_bev_gpu (mode SST_BOX_OVERLAP) and
+ * iou3d_cuda.boxes_iou_bev_gpu (mode SST_BOX_IOU) of mmdet3d/ops/iou3d/src/iou3d.cpp:34-78 (kernels
+ * iou3d_kernel.cu:127-282); SST_BOX_IOU_AXIS is the pairwise form of iou_normal (:335-343).
+ *   d_a [n_a, 5], d_b [n_b, 5] fp32; d_out [n_a, n_b] fp32, caller-owned, every element written.  No workspace.
+ *   PARITY: the arithmetic is restated from iou3d_kernel.cu (same operations and order, no contraction) and pinned to
+ *   the reference's own known-answer tests (tests/golden/box_ops_kat.npz), not to a run of that kernel. */
+int sst_boxes_overlap_bev_f32(const float* d_a, int64_t n_a, const float* d_b, int64_t n_b, int mode, float* d_out,
+                              void* stream);
+
+/* Aligned (1-to-1) BEV overlap: d_out[i] = value(d_a[i], d_b[i]) for the modes above.  Stands for TorchEx
+ * boxes_overlap_1to1 as called from core/bbox/structures/lidar_box3d.py:404-449, 505-549 (mode SST_BOX_OVERLAP).
+ *   d_a, d_b [n, 5] fp32; d_out [n] fp32, caller-owned.  Bit-identical to the diagonal of sst_boxes_overlap_bev_f32.
+ *   PARITY: the TorchEx contract inferred from lidar_box3d.py (its source is absent from the reference tree); the
+ *   per-pair arithmetic is that of sst_boxes_overlap_bev_f32. */
+int sst_boxes_overlap_aligned_f32(const float* d_a, const float* d_b, int64_t n, int mode, float* d_out, void* stream);
+
+/* NMS over boxes sorted by descending score.  Replaces iou3d_cuda.nms_gpu (rotated != 0) and nms_normal_gpu
+ * (rotated == 0) of mmdet3d/ops/iou3d/src/iou3d.cpp:95-185 (mask kernels iou3d_kernel.cu:284-333, 345-): box i
+ * suppresses a later box j when IoU(i, j) > threshold strictly; a box never suppresses itself.  Only the 64 x 64
+ * tiles on or above the diagonal of the mask are computed; the greedy sweep (the reference's host loop) runs on the
+ * device in one workgroup, so the mask never leaves the device.
+ *   d_sorted_boxes [n, 5] fp32.  d_group: NULL (one group, threshold `thresh`) or int32 [n] group ids: boxes suppress
+ *   only within their group, with the threshold h_group_thresh[g] (HOST fp32 [n_groups], 1 <= n_groups <= 64, passed
+ *   to the kernel as an argument; +inf = no suppression, no IoU computed; an id outside [0, n_groups) suppresses
+ *   nothing).
+ *   d_keep [n] int64 (caller-owned): the kept positions in ascending order, first *d_num_keep entries written.
+ *   d_num_keep: device int32 (the one value a caller reads back).  Workspace: sst_nms_bev_workspace_bytes(n)
+ *   (the [n, ceil(n / 64)] mask).  n <= 516096, else SST_ERR_UNSUPPORTED.
+ *   PARITY: the IoU arithmetic is restated from iou3d_kernel.cu and pinned to the reference's own known-answer tests
+ *   (tests/golden/box_ops_kat.npz, test_parta2_bbox_head.py's multi_class_nms), not to a run of that kernel. */
+int64_t sst_nms_bev_workspace_bytes(int64_t n);
+int sst_nms_bev_f32(const float* d_sorted_boxes, const int32_t* d_group, int64_t n, float thresh,
+                    const float* h_group_thresh, int n_groups, int rotated, int64_t* d_keep, int32_t* d_num_keep,
+                    void* d_workspace, void* stream);
+
+/* Points in boxes.  Replaces roiaware_pool3d_ext.points_in_boxes_gpu (mode SST_PIB_FIRST) and
+ * points_in_boxes_batch (mode SST_PIB_MEMBERSHIP) of mmdet3d/ops/roiaware_pool3d/src/points_in_boxes_cuda.cu:24-105.
+ *   d_boxes [batch, n_boxes, 7] fp32 LiDAR boxes, d_pts [batch, n_pts, 3] fp32.
+ *   d_out int32, caller-owned, every element written: [batch, n_pts] (first box index or -1) or
+ *   [batch, n_pts, n_boxes] (0 / 1).  No workspace.
+ *   PARITY: the membership test is dpp_classify of the dynamic point pool (csrc/pib_test.h), pinned to the reference's
+ *   compiled CPU routine points_in_boxes_cpu (tests/golden/point_pool.npz). */
+int sst_points_in_boxes_f32(const float* d_boxes, const float* d_pts, int batch, int64_t n_boxes, int64_t n_pts,
+                            int mode, int32_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,9 @@ from .sparse_unet import (SimpleSparseUNet, SparseBasicBlock, SparseUNet, Virtua
                           make_sparse_convmodule)
 
 from .virtual_voxel import VirtualVoxelExtractor  # noqa: F401
+from . import box_ops  # noqa: F401
+from .box_ops import (box3d_multiclass_nms, boxes3d_overlaps_lidar, boxes_iou_bev, boxes_overlap_1to1,  # noqa: F401
+                      boxes_overlap_bev, nms_gpu, nms_normal_gpu, points_in_boxes_batch, points_in_boxes_gpu)
 from . import detectors  # noqa: F401
 from .detectors import (DETECTORS, HEADS, NECKS, FSD, FSDV2, DynamicCenterPoint, DynamicVoxelNet, SingleStageFSD, SingleStageFSDV2, VoteSegHead,  # noqa: F401
                         VoteSegmentor, Voxel2PointScatterNeck, build_detector, build_head, build_model, build_neck,
@@ -53,4 +56,6 @@ __all__ = [
     'dynamic_point_pool', 'dynamic_point_pool_mixed', 'spconv', 'SparseConvTensor', 'SparseSequential', 'SparseModule',
     'SubMConv3d', 'SparseConv3d', 'SparseConvTranspose3d', 'SparseInverseConv3d', 'SparseMaxPool3d', 'SparseUNet', 'SimpleSparseUNet', 'VirtualVoxelMixer',
     'SparseBasicBlock', 'make_sparse_convmodule',
+    'box_ops', 'boxes_iou_bev', 'boxes_overlap_bev', 'boxes_overlap_1to1', 'nms_gpu', 'nms_normal_gpu',
+    'points_in_boxes_gpu', 'points_in_boxes_batch', 'boxes3d_overlaps_lidar', 'box3d_multiclass_nms',
 ]

@@ -4,8 +4,8 @@ constructs on the way from points to the features the heads consume, with the re
 sub-module names (-> ``state_dict`` keys) and data flow.  Every sub-config whose ``type`` this library implements is BUILT
 (Voxelization, DynamicScatterVFE, PseudoMiddleEncoderForSpconvFSD / SSTInputLayerV2, SimpleSparseUNet / SSTv2,
 Voxel2PointScatterNeck, VoteSegHead, SIR, ClusterAssigner, the virtual-voxel stage with multiscale_cfg / as_rpn,
-DynamicPointROIExtractor); the rest - box heads, losses, target assignment, box decoding, NMS: out of scope - is kept as
-its config under ``self.unbuilt`` and never run.  Nothing here computes a loss.
+DynamicPointROIExtractor); the rest - box heads, losses, target assignment, box decoding, NMS - is kept as
+its config under ``self.unbuilt`` and never run (the box ops those heads call are in ``sst_amd.box_ops``).  Nothing here computes a loss.
 
 Reference:
   VoteSegmentor            mmdet3d/models/detectors/single_stage_fsd.py:155-384 (__init__, voxelize, extract_feat, reorder,

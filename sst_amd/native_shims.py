@@ -7,6 +7,9 @@ every reference .py file stays as it is, only the compiled extensions are swappe
     sys.modules['dynamic_point_pool_ext'] = shims.dynamic_point_pool_ext        # TorchEx, dynamic_point_pool_op.py:36, 86-88
     sys.modules['mmdet3d.ops.spconv.sparse_conv_ext'] = shims.sparse_conv_ext   # ops/spconv/ops.py:93-183
     sys.modules['torch_scatter'] = shims.torch_scatter                          # sst_ops.py:172-177
+    sys.modules['mmdet3d.ops.iou3d.iou3d_cuda'] = shims.iou3d_cuda              # iou3d_utils.py, base_box3d.py:395-450
+    sys.modules['mmdet3d.ops.roiaware_pool3d.roiaware_pool3d_ext'] = shims.roiaware_pool3d_ext  # points_in_boxes.py
+    sys.modules['torchex'] = shims.torchex                                      # TorchEx, lidar_box3d.py:5-12
 
 Each namespace has exactly the functions, argument orders and in / out conventions of the module it stands for (outputs
 the reference pre-allocates are written in place).  Everything runs on the GPU through the C ABI of libsst_amd.so
@@ -18,6 +21,7 @@ import types
 import torch
 
 from . import _lib
+from . import box_ops as _box
 from . import kernels as K
 from . import spconv as _spconv
 from . import voxel as _voxel
@@ -152,3 +156,65 @@ def _scatter(src, index, dim=0, reduce='sum'):
 
 
 torch_scatter = types.SimpleNamespace(scatter_max=_scatter_max, scatter=_scatter)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# mmdet3d/ops/iou3d/iou3d_cuda  (src/iou3d.cpp:34-185)
+# ------------------------------------------------------------------------------------------------------------------
+def _fill_pairwise(mode, boxes_a, boxes_b, ans):
+    """ans: the caller's [M, N] fp32 device tensor, written in place (CHECK_INPUT on all three, iou3d.cpp:34-78)"""
+    _box._check_boxes(boxes_a, 5, 'iou3d_cuda')
+    _box._check_boxes(boxes_b, 5, 'iou3d_cuda')
+    _box._check_f32(ans)
+    if not ans.is_contiguous():
+        raise RuntimeError('iou3d_cuda: the output must be contiguous')
+    if tuple(ans.shape) != (boxes_a.size(0), boxes_b.size(0)):
+        raise RuntimeError(f'iou3d_cuda: output of shape {tuple(ans.shape)} for {boxes_a.size(0)} x {boxes_b.size(0)} boxes')
+    if ans.numel():
+        _lib.check(_lib.load().sst_boxes_overlap_bev_f32(_lib.ptr(boxes_a), boxes_a.size(0), _lib.ptr(boxes_b),
+                                                         boxes_b.size(0), mode, _lib.ptr(ans), _lib.stream_ptr()),
+                   'iou3d_cuda')
+    return 1
+
+
+def _nms_into(rotated, boxes, keep, nms_overlap_thresh, device_id=None):
+    """keep: the caller's CPU int64 [N] (iou3d.cpp:95-147): the first num_out entries are written; returns num_out"""
+    _box._check_boxes(boxes, 5, 'iou3d_cuda.nms')
+    if keep.is_cuda or keep.dtype != torch.int64 or not keep.is_contiguous() or keep.numel() < boxes.size(0):
+        raise RuntimeError('iou3d_cuda.nms: keep must be a contiguous CPU int64 tensor of at least N entries')
+    kept, num = _box.nms_sorted(boxes, nms_overlap_thresh, rotated=rotated)
+    if num:
+        keep[:num].copy_(kept)
+    return num
+
+
+iou3d_cuda = types.SimpleNamespace(
+    boxes_overlap_bev_gpu=lambda a, b, ans: _fill_pairwise(_box.BOX_OVERLAP, a, b, ans),
+    boxes_iou_bev_gpu=lambda a, b, ans: _fill_pairwise(_box.BOX_IOU, a, b, ans),
+    nms_gpu=lambda boxes, keep, thresh, device_id=None: _nms_into(True, boxes, keep, thresh, device_id),
+    nms_normal_gpu=lambda boxes, keep, thresh, device_id=None: _nms_into(False, boxes, keep, thresh, device_id))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# mmdet3d/ops/roiaware_pool3d/roiaware_pool3d_ext  (src/points_in_boxes_cuda.cu:24-105); boxes come first
+# ------------------------------------------------------------------------------------------------------------------
+def _not_ported(name):
+    def _raise(*args, **kwargs):
+        raise RuntimeError(f'roiaware_pool3d_ext.{name} is not provided by sst_amd: it has no caller on the SST / FSD '
+                           'path (RoIAwarePool3d is used by PartA2 only; points_in_boxes_cpu by data tools)')
+    return _raise
+
+
+roiaware_pool3d_ext = types.SimpleNamespace(
+    points_in_boxes_gpu=lambda boxes, pts, out: _box._points_in_boxes_into(boxes, pts, out, _box.PIB_FIRST),
+    points_in_boxes_batch=lambda boxes, pts, out: _box._points_in_boxes_into(boxes, pts, out, _box.PIB_MEMBERSHIP),
+    points_in_boxes_cpu=_not_ported('points_in_boxes_cpu'), forward=_not_ported('forward'),
+    backward=_not_ported('backward'))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# TorchEx: boxes_overlap_1to1 only.  `from torchex import connected_components` must keep raising ImportError: the
+# reference falls back to scipy on it (single_stage_fsd.py:19-22).
+# ------------------------------------------------------------------------------------------------------------------
+torchex = types.ModuleType('torchex', 'sst_amd stand-in for TorchEx: boxes_overlap_1to1 only')
+torchex.boxes_overlap_1to1 = _box.boxes_overlap_1to1
