@@ -1,5 +1,5 @@
-"""Host restatements of the rotated-box ops (csrc/box_ops.hip), for tests/test_box_ops_host.py and
-tests/test_gpu_box_ops.py.
+"""Host restatements of the rotated-box ops (csrc/box_ops.hip), for tests/test_box_ops_host.py,
+tests/test_gpu_box_ops.py, tests/test_box_ops_detector_host.py and tests/test_gpu_box_ops_detector.py.
 
 - bev_overlap_f32 / bev_iou_f32: the reference's polygon algorithm (ops/iou3d/src/iou3d_kernel.cu:54-251) in numpy
   float32, vectorised over pairs: the same operations in the same order, one rounding per product and sum.  The
@@ -10,7 +10,12 @@ tests/test_gpu_box_ops.py.
 - nms_host: the reference's greedy sweep (iou3d.cpp:116-133) over a float32 IoU, using only the pairs whose
   circumscribed circles meet (every other pair has IoU 0 exactly).
 - multiclass_nms_host: core/post_processing/box3d_nms.py:10-143 with that NMS.
+- detector_pairs / detector_boxes / detector_nms_inputs: inputs as a detection head emits them, with the noise bounds
+  measured on them (DETECTOR_IOU_NOISE, DETECTOR_AREA_NOISE); chain_boxes / periodic_boxes / dense_boxes: NMS inputs
+  with exact IoUs and analytic keep lists.
 """
+import functools
+
 import numpy as np
 
 F32 = np.float32
@@ -33,6 +38,229 @@ def random_pairs(n, seed):
     a = np.column_stack([ca - sa / 2, ca + sa / 2, ra]).astype(F32)
     b = np.column_stack([cb - sb / 2, cb + sb / 2, rb]).astype(F32)
     return a, b
+
+
+def cluster_boxes(n, seed, extent=75.0):
+    """boxes scattered uniformly within +-extent, sizes 0.5 - 6 m, any angle"""
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(-extent, extent, (n, 2))
+    s = rng.uniform(0.5, 6.0, (n, 2))
+    return np.column_stack([c - s / 2, c + s / 2, rng.uniform(-np.pi, np.pi, n)]).astype(F32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# detector-like inputs: clusters of near-duplicate boxes, as a detection head emits them
+# ---------------------------------------------------------------------------------------------------------------------
+DETECTOR_FAMILIES = ('jitter', 'same_angle', 'quarter_turn', 'tiny_angle', 'shift_only', 'axis0', 'big_angle',
+                     'identical')
+DETECTOR_SEED = 1  # the seed of every measurement below and of the tests that use the bounds
+
+# A pair is UNSTABLE when the float32 restatement is more than this from the float64 clip: the reference's polygon
+# algorithm itself lost or doubled a polygon point there (a corner on the 1e-5 in-box margin, a crossing of two
+# near-parallel edges), and one ulp in a sine decides on which side it lands.  No |1 - IoU| between 1e-4 and 1e-1 was
+# found over 36 000 identical-box pairs, so the cut separates the two populations.  Unstable pairs are excused, and
+# their share is bounded (UNSTABLE_SHARE_MAX): measured 0 for seven families and 0.95 % for `identical` (the reference's
+# algorithm returns IoU < 0.5 for 19 of 2000 identical boxes with centres within +-75 m at seed 1, 16 of 2000 at seed
+# 2, 94 of 20 000 at seed 3; parity with the reference is the contract, so this is documented and not repaired).
+UNSTABLE_GAP = 1e-3
+UNSTABLE_SHARE_MAX = 0.02
+
+# Largest |float32 restatement - float64 clip| of the BEV IoU over the STABLE pairs of detector_pairs(family, 2000,
+# DETECTOR_SEED), all eight families, measured on the CPU (numpy float32; the kernel is not involved):
+#   jitter 4.81e-5, same_angle 3.42e-5, quarter_turn 6.15e-5, tiny_angle 4.80e-5, shift_only 5.66e-5, axis0 1.50e-5,
+#   big_angle 5.19e-5, identical 2.25e-5 (19 of its 2000 pairs unstable, none in the other families)
+#   -> raw 6.15e-5, rounded up to 7e-5 (DETECTOR_IOU_MEASURED, what the host test holds the restatement to; seed 2
+#   gave 5.14e-5).  That is 7 x F32_IOU_NOISE, which was measured on random pairs only.
+# The device's sinf / cosf / atan2f are an independent draw of the same rounding noise, hence a margin of a factor 2
+# for the kernel against float64: 1.4e-4.
+DETECTOR_IOU_MEASURED = 7e-5
+DETECTOR_IOU_NOISE = 2 * DETECTOR_IOU_MEASURED
+# The same for the overlap area, relative to the area of the smaller box of the pair: raw 3.52e-5 (jitter; seed 2
+# gave 3.58e-5), rounded up to 4e-5, margin of a factor 2: 8e-5.
+DETECTOR_AREA_MEASURED = 4e-5
+DETECTOR_AREA_NOISE = 2 * DETECTOR_AREA_MEASURED
+
+
+def _detector_sizes(rng, n):
+    """(extent along x, extent along y) of vehicles, pedestrians and trucks: width 0.5 - 2.5 m, length 0.5 - 12 m"""
+    kind = rng.integers(0, 3, n)
+    length = np.choose(kind, [rng.uniform(3.5, 5.5, n), rng.uniform(0.5, 1.0, n), rng.uniform(6.0, 12.0, n)])
+    width = np.choose(kind, [rng.uniform(1.6, 2.2, n), rng.uniform(0.5, 0.9, n), rng.uniform(2.0, 2.5, n)])
+    return np.column_stack([length, width])
+
+
+def _xyxyr(c, s, r):
+    return np.column_stack([c - s / 2, c + s / 2, r]).astype(F32)
+
+
+def detector_pairs(family, n, seed):
+    """n pairs (a[i], b[i]) as a detector's near-duplicates of one object: centres within +-75 m, vehicle / pedestrian /
+    truck sizes.  Box b is box a with
+      jitter        centre sigma 0.15 m, size 3 %, angle sigma 0.05 rad
+      same_angle    the same size and angle, the centre shifted by up to half the size along both axes
+      quarter_turn  the angle + k pi / 2, k in -2 .. 2, centre sigma 0.15 m
+      tiny_angle    the angle +- 10^U(-7, -3), centre sigma 0.15 m
+      shift_only    the same size and angle, the centre shifted along ONE axis
+      axis0         both angles 0, centre and size jitter
+      big_angle     the jitter family with k 2 pi (|k| <= 20) added to either angle
+      identical     nothing changed: b = a"""
+    assert family in DETECTOR_FAMILIES, family
+    rng = np.random.default_rng([seed, DETECTOR_FAMILIES.index(family)])
+    ca = rng.uniform(-75, 75, (n, 2))
+    sa = _detector_sizes(rng, n)
+    ra = rng.uniform(-np.pi, np.pi, n)
+    cb, sb, rb = ca.copy(), sa.copy(), ra.copy()
+    near = rng.normal(0, 0.15, (n, 2))
+    if family in ('jitter', 'axis0', 'big_angle'):
+        cb = ca + near
+        sb = sa * (1 + rng.normal(0, 0.03, (n, 2)))
+        rb = ra + rng.normal(0, 0.05, n)
+    if family == 'same_angle':
+        cb = ca + rng.uniform(-0.5, 0.5, (n, 2)) * sa
+    elif family == 'quarter_turn':
+        cb = ca + near
+        rb = ra + rng.integers(-2, 3, n) * (np.pi / 2)
+    elif family == 'tiny_angle':
+        cb = ca + near
+        rb = ra + rng.choice([-1.0, 1.0], n) * 10.0 ** rng.uniform(-7, -3, n)
+    elif family == 'shift_only':
+        axis = rng.integers(0, 2, n)
+        cb[np.arange(n), axis] += rng.uniform(-1, 1, n) * sa[np.arange(n), axis]
+    elif family == 'axis0':
+        ra, rb = np.zeros(n), np.zeros(n)
+    elif family == 'big_angle':
+        ra = ra + rng.integers(-20, 21, n) * (2 * np.pi)
+        rb = rb + rng.integers(-20, 21, n) * (2 * np.pi)
+    over = np.sign(cb) * np.maximum(np.abs(cb) - 75, 0)  # a pair that left the range is moved back as a whole
+    a, b = _xyxyr(ca - over, sa, ra), _xyxyr(cb - over, sb, rb)
+    if family == 'identical':
+        b = a.copy()
+    return a, b
+
+
+_OBJECT_KINDS = np.array([[4.5, 1.9], [0.8, 0.6], [1.8, 0.7], [10.0, 2.5]])  # car, pedestrian, cyclist, truck
+
+
+def detector_boxes(n, seed):
+    """n boxes [x1, y1, x2, y2, ry] as the raw output of a detection head, for NMS: about n / 25 objects of four size
+    kinds, every box one of its object's near-duplicates (centre sigma 0.15 m, size 3 %, angle sigma 0.05 rad), 10 %
+    of them flipped by pi, 10 % exact copies of an earlier box of the same object.  The objects lie within
+    +-min(75, 3.5 sqrt(objects)) m, so neighbouring objects overlap now and then."""
+    rng = np.random.default_rng([seed, 1000])
+    n_obj = max(1, int(round(n / 25)))
+    extent = min(75.0, 3.5 * np.sqrt(n_obj))
+    oc = rng.uniform(-extent, extent, (n_obj, 2))
+    os_ = _OBJECT_KINDS[rng.integers(0, 4, n_obj)] * rng.uniform(0.85, 1.15, (n_obj, 2))
+    orot = rng.uniform(-np.pi, np.pi, n_obj)
+    obj = rng.integers(0, n_obj, n)
+    c = oc[obj] + rng.normal(0, 0.15, (n, 2))
+    s = os_[obj] * (1 + rng.normal(0, 0.03, (n, 2)))
+    r = orot[obj] + rng.normal(0, 0.05, n) + np.where(rng.random(n) < 0.1, np.pi, 0.0)
+    b = _xyxyr(c, s, r)
+    dup = rng.random(n) < 0.1
+    pick = rng.random(n)
+    seen = [[] for _ in range(n_obj)]
+    for i in range(n):
+        earlier = seen[obj[i]]
+        if dup[i] and earlier:
+            b[i] = b[earlier[int(pick[i] * len(earlier))]]
+        earlier.append(i)
+    return b
+
+
+@functools.lru_cache(maxsize=4)
+def _detector_frame(m, seed):
+    """m detector_boxes in a random score order with their compared pairs, judged once: (boxes, j of every pair,
+    unstable, float32 IoU, float64 IoU)"""
+    b = detector_boxes(m, seed)[np.random.default_rng([seed, 2000]).permutation(m)]
+    ii, jj = near_pairs(b)
+    unstable, iou64 = unstable_pairs(b[ii], b[jj])
+    return b, jj, unstable, bev_iou_f32(b[ii], b[jj]).astype(np.float64), iou64
+
+
+def detector_nms_inputs(n, thresh, seed):
+    """n detector_boxes in a random score order for rotated NMS at `thresh` -> (boxes [n, 5], share of the generated
+    boxes that was dropped).  Of every compared pair that is unstable, or whose IoU (float32 or float64) is within
+    2 x DETECTOR_IOU_NOISE of the threshold, the later box is dropped: the kernel and the host sweep may each differ by
+    DETECTOR_IOU_NOISE from float64 on the pairs that are left.  15 % extra boxes are generated so that n stays exact."""
+    m = int(n * 1.15) + 8
+    b, jj, unstable, iou32, iou64 = _detector_frame(m, seed)
+    bad = unstable | (np.abs(iou32 - thresh) <= 2 * DETECTOR_IOU_NOISE) | (np.abs(iou64 - thresh) <= 2 * DETECTOR_IOU_NOISE)
+    drop = np.zeros(m, bool)
+    drop[jj[bad]] = True
+    b = b[~drop]
+    assert len(b) >= n, (len(b), n)
+    return b[:n].copy(), drop.sum() / m
+
+
+def iou_f64_pairs(a, b):
+    """the float64 clip over pairs -> (IoU, overlap area), a Python loop (about 40 us per pair)"""
+    a64, b64 = np.asarray(a, np.float64).reshape(-1, 5), np.asarray(b, np.float64).reshape(-1, 5)
+    area = np.array([bev_overlap_f64(x, y) for x, y in zip(a64, b64)]).reshape(-1)
+    sa = (a64[:, 2] - a64[:, 0]) * (a64[:, 3] - a64[:, 1])
+    sb = (b64[:, 2] - b64[:, 0]) * (b64[:, 3] - b64[:, 1])
+    return area / np.maximum(sa + sb - area, 1e-8), area
+
+
+def smaller_area(a, b):
+    a64, b64 = np.asarray(a, np.float64).reshape(-1, 5), np.asarray(b, np.float64).reshape(-1, 5)
+    return np.minimum((a64[:, 2] - a64[:, 0]) * (a64[:, 3] - a64[:, 1]), (b64[:, 2] - b64[:, 0]) * (b64[:, 3] - b64[:, 1]))
+
+
+def unstable_pairs(a, b, iou64=None):
+    """the pairs whose float32 restatement is more than UNSTABLE_GAP from float64 -> (bool [N], float64 IoU [N]); the
+    host decides this, never a kernel's output"""
+    if iou64 is None:
+        iou64 = iou_f64_pairs(a, b)[0]
+    return np.abs(bev_iou_f32(a, b).astype(np.float64) - iou64) > UNSTABLE_GAP, iou64
+
+
+DETECTOR_PAIRS = 2000
+
+
+@functools.lru_cache(maxsize=None)
+def detector_family(family):
+    """the committed pairs of a family with their float64 reference, computed once and shared (read only)"""
+    a, b = detector_pairs(family, DETECTOR_PAIRS, DETECTOR_SEED)
+    iou64, area64 = iou_f64_pairs(a, b)
+    return dict(a=a, b=b, iou64=iou64, area64=area64, small=smaller_area(a, b),
+                unstable=unstable_pairs(a, b, iou64)[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# structured NMS inputs with analytic keep lists: axis-aligned boxes whose IoUs are exact in float32
+# ---------------------------------------------------------------------------------------------------------------------
+HALF_PAIR = np.array([[0, 0, 2, 2, 0], [0, 0, 2, 1, 0]], F32)  # IoU exactly 0.5, rotated and axis mode
+BELOW_HALF = float(np.nextafter(F32(0.5), F32(0)))              # the largest float32 below 0.5
+
+
+def chain_boxes(n):
+    """box i = [0.25 i, 0, 0.25 i + 1, 1]: neighbours have IoU 0.75 / 1.25 = 0.6, boxes two apart 0.5 / 1.5 = 1 / 3; at
+    threshold 0.5 every kept box removes exactly its successor -> (boxes, keep = the even positions)"""
+    x = F32(0.25) * np.arange(n, dtype=F32)
+    z = np.zeros(n, F32)
+    return np.column_stack([x, z, x + F32(1), z + F32(1), z]).astype(F32), np.arange(0, n, 2)
+
+
+def slot_boxes(slots):
+    """unit boxes on a grid of pitch 2 (100 per row): equal slots are identical boxes (IoU 1), different slots are disjoint
+    (IoU 0).  The grid keeps every coordinate below 256: from there on x - 1e-5 rounds to x in float32, and the
+    reference's in-box test no longer finds a corner of an identical box."""
+    slots = np.asarray(slots)
+    assert slots.max(initial=0) < 100 * 127
+    x, y = F32(2) * (slots % 100).astype(F32), F32(2) * (slots // 100).astype(F32)
+    return np.column_stack([x, y, x + F32(1), y + F32(1), np.zeros(len(x), F32)]).astype(F32)
+
+
+def periodic_boxes(n, period):
+    """box i is a copy of box i mod period -> (boxes, keep = range(period)); with period 70 every 64-column word of the
+    mask has its own bit pattern and each kept row's copies lie in every later column block"""
+    return slot_boxes(np.arange(n) % period), np.arange(min(n, period))
+
+
+def dense_boxes(n):
+    """n identical boxes: every mask word is full -> (boxes, keep = [0])"""
+    return slot_boxes(np.zeros(n, np.int64)), np.arange(min(n, 1))
 
 
 def _rot(cx, cy, cs, sn, x, y):
@@ -246,6 +474,21 @@ def nms_host(sorted_boxes, thresh, rotated=True, groups=None, group_thresh=None,
             keep.append(i)
             removed[succ[i]] = True
     return np.array(keep, np.int64)
+
+
+def nms_inputs(n, thresh, rotated, seed):
+    """sorted boxes with no compared pair's IoU within 1e-4 of the threshold(s): the later box of such a pair is
+    dropped (the pairs among the boxes that stay are a subset of the pairs judged, so one pass is enough)"""
+    thresholds = np.atleast_1d(np.asarray(thresh, F32))
+    extent = max(8.0, np.sqrt(max(n, 1)) * 1.2)
+    b = cluster_boxes(int(n * 1.1) + 4, seed, extent)
+    fn = bev_iou_f32 if rotated else axis_iou_f32
+    ii, jj = near_pairs(b)
+    iou = fn(b[ii], b[jj]) if len(ii) else np.zeros(0, F32)
+    bad = (np.abs(iou[:, None] - thresholds[None]) < 1e-4).any(1)
+    drop = np.zeros(len(b), bool)
+    drop[jj[bad]] = True
+    return b[~drop][:n]
 
 
 def multiclass_nms_host(bboxes, bboxes_for_nms, scores, score_thr, max_num, nms_thr, rotated,

@@ -22,11 +22,8 @@ def _t(a, dtype=torch.float32):
     return torch.as_tensor(np.asarray(a)).to(device=DEV, dtype=dtype).contiguous()
 
 
-def _cluster_boxes(n, seed, extent=75.0):
-    rng = np.random.default_rng(seed)
-    c = rng.uniform(-extent, extent, (n, 2))
-    s = rng.uniform(0.5, 6.0, (n, 2))
-    return np.column_stack([c - s / 2, c + s / 2, rng.uniform(-np.pi, np.pi, n)]).astype(F32)
+_cluster_boxes = R.cluster_boxes
+_nms_inputs = R.nms_inputs
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -92,24 +89,6 @@ def test_empty_and_zero_area():
 # ---------------------------------------------------------------------------------------------------------------------
 # NMS
 # ---------------------------------------------------------------------------------------------------------------------
-def _nms_inputs(n, thresh, rotated, seed):
-    """sorted boxes with no compared pair's IoU within 1e-4 of the threshold(s) (boxes of such pairs are dropped)"""
-    thresholds = np.atleast_1d(np.asarray(thresh, F32))
-    extent = max(8.0, np.sqrt(max(n, 1)) * 1.2)
-    b = _cluster_boxes(int(n * 1.1) + 4, seed, extent)
-    fn = R.bev_iou_f32 if rotated else R.axis_iou_f32
-    for _ in range(5):
-        ii, jj = R.near_pairs(b)
-        iou = fn(b[ii], b[jj]) if len(ii) else np.zeros(0, F32)
-        bad = (np.abs(iou[:, None] - thresholds[None]) < 1e-4).any(1)
-        if not bad.any():
-            break
-        drop = np.zeros(len(b), bool)
-        drop[jj[bad]] = True
-        b = b[~drop]
-    return b[:n]
-
-
 @pytest.mark.parametrize('rotated', [True, False])
 def test_nms_keep_lists_equal_the_host_sweep(rotated):
     from sst_amd import box_ops
