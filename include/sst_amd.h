@@ -1178,6 +1178,59 @@ int sst_nms_bev_f32(const float* d_sorted_boxes, const int32_t* d_group, int64_t
 int sst_points_in_boxes_f32(const float* d_boxes, const float* d_pts, int batch, int64_t n_boxes, int64_t n_pts,
                             int mode, int32_t* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Furthest point sampling and FSD's SSG cluster assignment (csrc/fps.hip).  fp32, deterministic, everything on `stream`.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_SSG_MULTI_BALL 1     /* status: some point lay in more than one ball                                  */
+#define SST_SSG_EMPTY_SEGMENT 2  /* status: some non-empty segment assigned no point                              */
+#define SST_SSG_BAD_KEYPOINT 4   /* status: a keypoint index outside its segment was skipped                      */
+
+/* Furthest point sampling inside each of n_segments segments of a point array.  Replaces
+ * furthest_point_sample_ext.furthest_point_sampling_wrapper of mmdet3d/ops/furthest_point_sample/src/
+ * furthest_point_sample.cpp (kernel furthest_point_sample_cuda.cu:25-141), one segment per batch entry, and the
+ * `if num_fps >= len(points)` branch of ssg_single_sample (detectors/single_stage_fsd.py:103-106).
+ *   d_points [n_points, >= 3] fp32 with row stride ld (columns 0..2 are read).
+ *   Segments: d_seg_offsets int32 [n_segments + 1] on the device, or NULL for n_segments segments of uniform_len points.
+ *   d_idx int32 [n_segments, m]: sample j of segment s, RELATIVE to the segment's first point.  Sample 0 is point 0,
+ *   sample j the arg-max of temp[k] = min(temp[k], d(k, sample j-1)), temp starting at 1e10 and
+ *   d = (x2-x1)*(x2-x1) + (y2-y1)*(y2-y1) + (z2-z1)*(z2-z1) evaluated left to right, every operation rounded on its own.
+ *   Among equal distances the reference's winner is kept: the k with the smallest
+ *   (bitreverse_{log2 B}(k mod B), k div B), B = max(min(2^floor(log2 n_s), 1024), 1) from the segment's length n_s.
+ *   identity_if_short != 0: a segment with n_s <= m gets 0 .. n_s-1 in order (then -1), d_count[s] = n_s.  Otherwise the
+ *   recurrence simply runs on when m > n_s (repeats, as in the reference) and d_count[s] = m.  An empty segment: a row of
+ *   -1 and d_count[s] = 0.  d_count (int32 [n_segments]) may be NULL.
+ *   d_temp fp32 [n_points]: workspace of the segments longer than 16 384 points (initialised here, used for the points
+ *   behind the first 12 288 of such a segment); shorter ones keep their state in registers and leave it untouched.  No
+ *   launch when n_segments == 0 or m == 0.
+ *   NaN / infinite coordinates are outside the contract. */
+int sst_fps_segmented_f32(const float* d_points, int64_t ld, int64_t n_points, const int32_t* d_seg_offsets,
+                          int64_t uniform_len, int64_t n_segments, int m, int identity_if_short, float* d_temp,
+                          int32_t* d_idx, int32_t* d_count, void* stream);
+
+/* The same selection with the distance to the last sample read from row `old` of a [batch, n, n] matrix (values >= 0).
+ * Replaces furthest_point_sampling_with_dist_wrapper (furthest_point_sample_cuda.cu:213-331).  d_temp fp32 [batch, n],
+ * d_idx int32 [batch, m]. */
+int sst_fps_with_dist_f32(const float* d_dist, int64_t batch, int64_t n, int m, float* d_temp, int32_t* d_idx,
+                          void* stream);
+
+/* Everything after the sampling in ssg_single_sample (detectors/single_stage_fsd.py:108-142) and the running base of
+ * ssg() (:83-97), for all segments at once.  Keypoint j of segment s is the point d_key_idx[s * m + j] (relative to the
+ * segment), j < d_key_count[s] (the outputs of sst_fps_segmented_f32).
+ *   Pruning: keypoint j falls if ANY earlier keypoint i < j of its segment - fallen ones included - has
+ *   sqrt(dx*dx + dy*dy) < thr2.  Numbering: a surviving keypoint's id = its rank among the survivors of its segment + the
+ *   survivors of all earlier segments.  Assignment: d_cluster_id[p] = the id of the one surviving keypoint of p's segment
+ *   with sqrt(dx*dx + dy*dy) < radius, or -1 if there is none or more than one.  thr2 and radius are the reference's
+ *   Python scalars (radius * 2 + 0.01, radius) rounded to fp32 by the caller; sum and square root are computed as written,
+ *   correctly rounded.
+ *   d_points [n_points, >= 2] fp32 with row stride ld; d_seg_offsets int32 [n_segments + 1] (n_segments <= 65535).
+ *   d_cluster_id int32 [n_points]; d_n_clusters, d_status: device int32 (SST_SSG_* bits; the first two are the
+ *   reference's asserts :125 and :128).  Workspace: sst_ssg_assign_workspace_bytes(n_segments, m). */
+int64_t sst_ssg_assign_workspace_bytes(int64_t n_segments, int m);
+int sst_ssg_assign_f32(const float* d_points, int64_t ld, int64_t n_points, const int32_t* d_seg_offsets,
+                       int64_t n_segments, const int32_t* d_key_idx, const int32_t* d_key_count, int m, float thr2,
+                       float radius, int32_t* d_cluster_id, int32_t* d_n_clusters, int32_t* d_status, void* d_workspace,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

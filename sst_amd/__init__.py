@@ -19,8 +19,10 @@ from .voxel_encoder import DynamicScatterVFE, DynamicVFE, DynamicVFELayer, Dynam
 from .sst_input_layer import PseudoMiddleEncoderForSpconvFSD, SSTInputLayer, SSTInputLayerV2
 from .sst_basic_block import BasicShiftBlockV2, EncoderLayer, WindowAttention
 from .backbones import SIR, SSTv1, SSTv2
-from .cluster import (ClusterAssigner, connected_components_xy, filter_almost_empty, find_connected_componets,  # noqa: F401
-                      find_connected_componets_single_batch, modify_cluster_by_class)
+from .cluster import (ClusterAssigner, HybridAssigner, SSGAssigner, connected_components_xy, filter_almost_empty,  # noqa: F401
+                      find_connected_componets, find_connected_componets_single_batch, modify_cluster_by_class, ssg,
+                      ssg_single_sample)
+from .fps import fps_segmented, furthest_point_sample, furthest_point_sample_with_dist, ssg_assign  # noqa: F401
 from .dynamic_point_pool import DynamicPointROIExtractor, dynamic_point_pool, dynamic_point_pool_mixed
 from . import spconv  # noqa: F401  (sst_amd.spconv mirrors mmdet3d.ops.spconv)
 from .spconv import (SparseConv3d, SparseConvTensor, SparseConvTranspose3d, SparseInverseConv3d,  # noqa: F401
@@ -58,4 +60,6 @@ __all__ = [
     'SparseBasicBlock', 'make_sparse_convmodule',
     'box_ops', 'boxes_iou_bev', 'boxes_overlap_bev', 'boxes_overlap_1to1', 'nms_gpu', 'nms_normal_gpu',
     'points_in_boxes_gpu', 'points_in_boxes_batch', 'boxes3d_overlaps_lidar', 'box3d_multiclass_nms',
+    'furthest_point_sample', 'furthest_point_sample_with_dist', 'fps_segmented', 'ssg_assign', 'ssg', 'ssg_single_sample',
+    'SSGAssigner', 'HybridAssigner',
 ]

@@ -300,6 +300,11 @@ _SIGNATURES = {
     'sst_nms_bev_workspace_bytes': (c_i64, [c_i64]),
     'sst_nms_bev_f32': (c_i32, [c_ptr, c_ptr, c_i64, c_f32, c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_points_in_boxes_f32': (c_i32, [c_ptr, c_ptr, c_i32, c_i64, c_i64, c_i32, c_ptr, c_ptr]),
+    'sst_fps_segmented_f32': (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_fps_with_dist_f32': (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
+    'sst_ssg_assign_workspace_bytes': (c_i64, [c_i64, c_i32]),
+    'sst_ssg_assign_f32': (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i32, c_f32, c_f32, c_ptr, c_ptr, c_ptr,
+                                   c_ptr, c_ptr]),
     'sst_event_create': (c_ptr, []),
     'sst_event_destroy': (None, [c_ptr]),
     'sst_event_elapsed_ms': (ctypes.c_float, [c_ptr, c_ptr]),

@@ -8,10 +8,17 @@ Reference cost being removed: per class and per sample a dense N x N distance ma
 connected_components on the CPU and a host->device copy (the documented source of FSD's training-time instability,
 docs/overall_instructions.md:51).  Here one lock-free union-find launch over all samples (csrc/cluster.hip); labels
 are bit-identical (components numbered by their smallest member, scipy's order of first appearance).
+
+``fps`` / ``ssg_single_sample`` / ``ssg`` (:24-28, :83-142), ``SSGAssigner`` (:1002-1101) and ``HybridAssigner``
+(:1104-1194) are the reference's other two assigner branches.  Reference cost being removed: a strictly sequential
+sampling kernel with ten barriers per sample, three dense matrices ([K, K], [K, N] distances and the [K, N] mask),
+nonzero, a sort and one read-back per assert, and in the hybrid assigner a Python loop over the samples.  Here one
+sampling launch and one assignment launch sequence for all samples of a class (csrc/fps.hip), and one read-back.
 """
 import torch
 
 from . import _lib
+from . import fps as _fps
 from . import kernels as K
 from .sst_ops import scatter_v2
 
@@ -122,37 +129,44 @@ class ClusterAssigner(torch.nn.Module):
         cell = K.const_tensor(self._per_class(self.cluster_voxel_size, class_name), dev, points.dtype)
         origin = K.const_tensor(self.point_cloud_range[:3], dev, points.dtype)
         cells = torch.cat([batch_idx[:, None], torch.div(points - origin, cell, rounding_mode='floor').int()], dim=1)
-        n = points.size(0)
-        if n == 0:
-            empty = torch.zeros((0, 2), dtype=torch.int32, device=dev)
-            return empty, torch.zeros(0, dtype=torch.bool, device=dev)
-        groups = K.unique_rows(cells.contiguous())
-        occupancy = groups.counts()                                         # votes per cluster voxel, sorted-voxel order
-        crowded = occupancy >= self.min_points
-        point_group = groups.inverse.long()
-        valid_mask = crowded[point_group]
-        sizes = torch.stack([valid_mask.sum(), crowded.sum()]).tolist()     # the one read-back of this class
-        if sizes[0] == 0:
-            # nothing survives the filter: the reference then keeps EVERY point (valid_mask = ~valid_mask, :968-970)
-            valid_mask = torch.ones_like(valid_mask)
-            crowded = torch.ones_like(crowded)
-            sizes = [n, groups.m]
-        keep_points = _nonzero_known(valid_mask, sizes[0])
-        keep_groups = _nonzero_known(crowded, sizes[1])
-        # centroids of the surviving voxels: the mean over ALL votes of a voxel (a voxel survives or falls as a whole)
-        centroids = K.segment_reduce(points.float().contiguous(), groups, 'mean').index_select(0, keep_groups)
-        centroid_sample = K.unpack_unique_rows(groups, torch.int32).index_select(0, keep_groups)[:, 0]
-        dist = self._per_class(self.connected_dist, class_name)
-        if self.training:
-            component = connected_components_xy(centroids, centroid_sample, dist)   # sorted-unique order = sample after sample
-        else:
-            # the reference's test path clusters all samples as one graph (both of its variants, :36-43 / :70-84)
-            component = find_connected_componets_single_batch(centroids, centroid_sample, dist)
-        assert component.numel() == sizes[1]
-        rank_of_group = torch.cumsum(crowded.int(), 0) - 1                   # surviving voxel -> row of `centroids`
-        point_component = component[rank_of_group[point_group[keep_points]].long()]
-        valid_mask._sst_keep = keep_points     # the indices of the set entries ride along: callers need not search again
-        return torch.stack([batch_idx[keep_points], point_component.int()], 1), valid_mask
+        # the reference's test path clusters all samples as one graph (both of its variants, :36-43 / :70-84)
+        return _ccl_single_class(points, batch_idx, cells, self.min_points, self._per_class(self.connected_dist, class_name),
+                                 per_sample=self.training)
+
+
+def _ccl_single_class(points, batch_idx, cells, min_points, dist, per_sample):
+    """the grouping -> filter -> centroids -> components -> points chain of ClusterAssigner.forward_single_class and
+    HybridAssigner.forward_ccl; ``cells`` [N, 4] = (sample, cluster-voxel coordinates) in the caller's column order"""
+    dev = points.device
+    n = points.size(0)
+    if n == 0:
+        empty = torch.zeros((0, 2), dtype=batch_idx.dtype, device=dev)
+        return empty, torch.zeros(0, dtype=torch.bool, device=dev)
+    groups = K.unique_rows(cells.contiguous())
+    occupancy = groups.counts()                                         # votes per cluster voxel, sorted-voxel order
+    crowded = occupancy >= min_points
+    point_group = groups.inverse.long()
+    valid_mask = crowded[point_group]
+    sizes = torch.stack([valid_mask.sum(), crowded.sum()]).tolist()     # the one read-back of this class
+    if sizes[0] == 0:
+        # nothing survives the filter: the reference then keeps EVERY point (valid_mask = ~valid_mask, :968-970)
+        valid_mask = torch.ones_like(valid_mask)
+        crowded = torch.ones_like(crowded)
+        sizes = [n, groups.m]
+    keep_points = _nonzero_known(valid_mask, sizes[0])
+    keep_groups = _nonzero_known(crowded, sizes[1])
+    # centroids of the surviving voxels: the mean over ALL votes of a voxel (a voxel survives or falls as a whole)
+    centroids = K.segment_reduce(points.float().contiguous(), groups, 'mean').index_select(0, keep_groups)
+    centroid_sample = K.unpack_unique_rows(groups, torch.int32).index_select(0, keep_groups)[:, 0]
+    if per_sample:
+        component = connected_components_xy(centroids, centroid_sample, dist)   # sorted-unique order = sample after sample
+    else:
+        component = find_connected_componets_single_batch(centroids, centroid_sample, dist)
+    assert component.numel() == sizes[1]
+    rank_of_group = torch.cumsum(crowded.int(), 0) - 1                   # surviving voxel -> row of `centroids`
+    point_component = component[rank_of_group[point_group[keep_points]].long()]
+    valid_mask._sst_keep = keep_points     # the indices of the set entries ride along: callers need not search again
+    return torch.stack([batch_idx[keep_points], point_component.to(batch_idx.dtype)], 1), valid_mask
 
 
 def _nonzero_known(mask, count):
@@ -160,3 +174,168 @@ def _nonzero_known(mask, count):
     if hasattr(torch, 'nonzero_static'):
         return torch.nonzero_static(mask, size=int(count)).squeeze(1)
     return torch.nonzero(mask).squeeze(1)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# furthest point sampling + ball assignment: SSGAssigner / HybridAssigner
+# ----------------------------------------------------------------------------------------------------------------------
+def fps(points, N):
+    """the N furthest-point samples of points [n, 3], as rows (single_stage_fsd.py:24-28)"""
+    idx = _fps.furthest_point_sample(points.unsqueeze(0), N)
+    idx = idx.squeeze(0).long()
+    return points[idx]
+
+
+def _ssg_segments(points, seg_offsets, num_fps, radius):
+    """sampling + pruning + numbering + assignment inside every segment of ``points``: two native calls, nothing read back.
+    -> (ids int32 [n], n_clusters int32 [1], status int32 [1])"""
+    pts = points.float()
+    if pts.dim() != 2 or (pts.size(0) > 0 and pts.stride(1) != 1):
+        pts = pts.contiguous()
+    key_idx, key_count = _fps.fps_segmented(pts, seg_offsets, num_fps, identity_if_short=True)
+    return _fps.ssg_assign(pts, seg_offsets, key_idx, key_count, radius * 2 + 0.01, radius)
+
+
+def _one_segment(n, device):
+    return torch.tensor([0, n], dtype=torch.int32, device=device)
+
+
+def _segments_of_sorted(batch_sorted, n_samples):
+    """offsets [n_samples + 1] of the runs of an ascending int32 sample-index vector"""
+    marks = torch.arange(n_samples + 1, dtype=torch.int32, device=batch_sorted.device)
+    return torch.searchsorted(batch_sorted.contiguous(), marks).int()
+
+
+def ssg_single_sample(points, num_fps, radius):
+    """single_stage_fsd.py:99-142: cluster id per point (-1: in no ball), int64"""
+    if not points.is_cuda:
+        raise RuntimeError('sst_amd.ssg_single_sample: CUDA tensors required (no CPU fallback)')
+    ids, _, status = _ssg_segments(points, _one_segment(points.size(0), points.device), num_fps, radius)
+    if points.size(0):
+        _fps.raise_on_status(status.item())
+    return ids.long()
+
+
+def ssg(points, batch_idx, num_fps, radius):
+    """single_stage_fsd.py:83-97 as ONE segmented call: the samples are the segments, the ids run on from sample to
+    sample.  Two read-backs: the number of samples (with the order check) and the status word."""
+    if not points.is_cuda:
+        raise RuntimeError('sst_amd.ssg: CUDA tensors required (no CPU fallback)')
+    n = points.size(0)
+    if n == 0:
+        return torch.zeros_like(batch_idx)
+    b = batch_idx.int()
+    ascending = (b[1:] >= b[:-1]).all() if n > 1 else torch.ones((), dtype=torch.bool, device=b.device)
+    n_samples, sorted_already = torch.stack([b.max() + 1, ascending.to(b.dtype)]).tolist()
+    if sorted_already:
+        ids, _, status = _ssg_segments(points, _segments_of_sorted(b, n_samples), num_fps, radius)
+    else:
+        # as find_connected_componets: bring the samples one after the other (stable), label, put back
+        order = torch.sort(b, stable=True)[1]
+        sorted_ids, _, status = _ssg_segments(points[order], _segments_of_sorted(b[order], n_samples), num_fps, radius)
+        ids = torch.empty_like(sorted_ids)
+        ids[order] = sorted_ids
+    _fps.raise_on_status(status.item())
+    return ids.to(batch_idx.dtype)
+
+
+def _zyx_cells(points, batch_idx, cluster_vsize, point_cloud_range):
+    """(sample, z, y, x) int64 cluster-voxel coordinates, as both assigners below form them (:1047-1051)"""
+    dev = points.device
+    cell = K.const_tensor(cluster_vsize, dev, points.dtype)
+    origin = K.const_tensor(point_cloud_range[:3], dev, points.dtype)
+    coors = torch.div(points - origin, cell, rounding_mode='floor').long()
+    return torch.cat([batch_idx.long()[:, None], coors[:, [2, 1, 0]]], dim=1)
+
+
+def _ssg_single_class(points, batch_idx, cells, num_fps, radius, per_sample):
+    """cluster-voxel means -> ssg over them -> every point inherits its voxel's id; points whose voxel got none are
+    dropped.  ONE read-back: the number of surviving points and the status word."""
+    dev = points.device
+    if points.size(0) == 0:
+        return torch.zeros((0, 2), dtype=torch.long, device=dev), torch.zeros(0, dtype=torch.bool, device=dev)
+    groups = K.unique_rows(cells.contiguous())
+    voxels = K.segment_reduce(points.float().contiguous(), groups, 'mean')
+    if per_sample:
+        if groups.mins[0] < 0:
+            raise RuntimeError('sst_amd: negative sample index')
+        voxel_sample = K.unpack_unique_rows(groups, torch.int32)[:, 0]          # sorted-unique: sample after sample
+        segments = _segments_of_sorted(voxel_sample, groups.mins[0] + groups.extents[0])
+    else:
+        segments = _one_segment(groups.m, dev)
+    ids, _, status = _ssg_segments(voxels, segments, num_fps, radius)
+    ids_per_point = ids[groups.inverse.long()]
+    valid_pts_mask = ids_per_point > -1
+    n_valid, status = torch.stack([valid_pts_mask.sum(), status[0].long()]).tolist()
+    _fps.raise_on_status(status)
+    keep = _nonzero_known(valid_pts_mask, n_valid)
+    valid_pts_mask._sst_keep = keep
+    return torch.stack([batch_idx.long()[keep], ids_per_point[keep].long()], 1), valid_pts_mask
+
+
+class SSGAssigner(torch.nn.Module):
+    """Furthest-point keypoints over the cluster-voxel means, pruned to non-overlapping balls; a point belongs to the one
+    ball its voxel's mean falls in (single_stage_fsd.py:1002-1101; same constructor and forward).  As in the reference the
+    sample index plays no part in sampling, pruning and assignment: ONE segment over all samples, the batch column only
+    rides along in the output."""
+
+    def __init__(self, cluster_voxel_size, point_cloud_range, radius, num_fps, class_names=['Car', 'Cyclist', 'Pedestrian']):
+        super().__init__()
+        self.cluster_voxel_size = cluster_voxel_size
+        self.radius = radius
+        self.num_fps = num_fps
+        self.point_cloud_range = point_cloud_range
+        self.class_names = class_names
+        self.num_classes = len(class_names)
+
+    _per_class = ClusterAssigner._per_class
+
+    @torch.no_grad()
+    def forward(self, points_list, batch_idx_list, gt_bboxes_3d=None, gt_labels_3d=None, origin_points=None):
+        assert self.num_classes == len(self.class_names)
+        outs = [self.forward_single_class(p, b, c, origin_points)
+                for p, b, c in zip(points_list, batch_idx_list, self.class_names)]
+        return modify_cluster_by_class([o[0] for o in outs]), [o[1] for o in outs]
+
+    def forward_single_class(self, points, batch_idx, class_name, origin_points):
+        cells = _zyx_cells(points, batch_idx, self._per_class(self.cluster_voxel_size, class_name), self.point_cloud_range)
+        return _ssg_single_class(points, batch_idx, cells, self.num_fps[class_name], self._per_class(self.radius, class_name),
+                                 per_sample=False)
+
+
+class HybridAssigner(torch.nn.Module):
+    """Per class either the ball assignment above, sample by sample (``assigner_type='ssg'``), or ClusterAssigner's
+    connected components (``'ccl'``) (single_stage_fsd.py:1104-1194; same constructor and methods).  As in the reference
+    both branches group by int64 (sample, z, y, x) coordinates and the ccl branch always labels per sample, whatever
+    ``self.training`` says."""
+
+    def __init__(self, point_cloud_range, cfg_per_class, class_names=['Car', 'Cyclist', 'Pedestrian']):
+        super().__init__()
+        self.point_cloud_range = point_cloud_range
+        self.class_names = class_names
+        self.cfg_per_class = cfg_per_class
+        self.num_classes = len(class_names)
+
+    @torch.no_grad()
+    def forward(self, points_list, batch_idx_list, gt_bboxes_3d=None, gt_labels_3d=None, origin_points=None):
+        assert self.num_classes == len(self.class_names)
+        outs = [self.forward_single_class(p, b, c, origin_points)
+                for p, b, c in zip(points_list, batch_idx_list, self.class_names)]
+        return modify_cluster_by_class([o[0] for o in outs]), [o[1] for o in outs]
+
+    def forward_single_class(self, points, batch_idx, class_name, origin_points):
+        assigner_type = self.cfg_per_class[class_name]['assigner_type']
+        if assigner_type == 'ssg':
+            return self.forward_ssg(points, batch_idx, class_name, origin_points)
+        elif assigner_type == 'ccl':
+            return self.forward_ccl(points, batch_idx, class_name, origin_points)
+
+    def forward_ssg(self, points, batch_idx, class_name, origin_points):
+        cfg = self.cfg_per_class[class_name]
+        cells = _zyx_cells(points, batch_idx, cfg['cluster_voxel_size'], self.point_cloud_range)
+        return _ssg_single_class(points, batch_idx, cells, cfg['num_fps'], cfg['radius'], per_sample=True)
+
+    def forward_ccl(self, points, batch_idx, class_name, origin_points):
+        cfg = self.cfg_per_class[class_name]
+        cells = _zyx_cells(points, batch_idx, cfg['cluster_voxel_size'], self.point_cloud_range)
+        return _ccl_single_class(points, batch_idx.long(), cells, cfg['min_points'], cfg['connected_dist'], per_sample=True)

@@ -3,7 +3,7 @@
 constructs on the way from points to the features the heads consume, with the reference's constructor arguments,
 sub-module names (-> ``state_dict`` keys) and data flow.  Every sub-config whose ``type`` this library implements is BUILT
 (Voxelization, DynamicScatterVFE, PseudoMiddleEncoderForSpconvFSD / SSTInputLayerV2, SimpleSparseUNet / SSTv2,
-Voxel2PointScatterNeck, VoteSegHead, SIR, ClusterAssigner, the virtual-voxel stage with multiscale_cfg / as_rpn,
+Voxel2PointScatterNeck, VoteSegHead, SIR, ClusterAssigner / SSGAssigner / HybridAssigner, the virtual-voxel stage with multiscale_cfg / as_rpn,
 DynamicPointROIExtractor); the rest - box heads, losses, target assignment, box decoding, NMS - is kept as
 its config under ``self.unbuilt`` and never run (the box ops those heads call are in ``sst_amd.box_ops``).  Nothing here computes a loss.
 
@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from . import kernels as K
-from .cluster import ClusterAssigner
+from .cluster import ClusterAssigner, HybridAssigner, SSGAssigner
 from .registry import BACKBONES, MODELS, ROI_EXTRACTORS, Registry, build_backbone, build_middle_encoder, build_voxel_encoder
 from .sst_ops import build_mlp, scatter_v2
 from .virtual_voxel import VirtualVoxelExtractor
@@ -389,9 +389,13 @@ class SingleStageFSD(_HotPathDetector):
             self.voxel_encoder = build_voxel_encoder(voxel_encoder)
         if middle_encoder is not None:
             self.middle_encoder = build_middle_encoder(middle_encoder)
-        if 'radius' in cluster_assigner or 'hybrid' in cluster_assigner:
-            raise NotImplementedError('SSGAssigner / HybridAssigner (furthest point sampling) are not on the path')
-        self.cluster_assigner = ClusterAssigner(**cluster_assigner)
+        if 'radius' in cluster_assigner:                                     # single_stage_fsd.py:429-435
+            self.cluster_assigner = SSGAssigner(**cluster_assigner)
+        elif 'hybrid' in cluster_assigner:
+            cluster_assigner.pop('hybrid')
+            self.cluster_assigner = HybridAssigner(**cluster_assigner)
+        else:
+            self.cluster_assigner = ClusterAssigner(**cluster_assigner)
         self.cluster_assigner.num_classes = self.num_classes
 
     def extract_feat(self, points, pts_feats, pts_cluster_inds, img_metas, center_preds):

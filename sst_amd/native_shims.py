@@ -10,6 +10,8 @@ every reference .py file stays as it is, only the compiled extensions are swappe
     sys.modules['mmdet3d.ops.iou3d.iou3d_cuda'] = shims.iou3d_cuda              # iou3d_utils.py, base_box3d.py:395-450
     sys.modules['mmdet3d.ops.roiaware_pool3d.roiaware_pool3d_ext'] = shims.roiaware_pool3d_ext  # points_in_boxes.py
     sys.modules['torchex'] = shims.torchex                                      # TorchEx, lidar_box3d.py:5-12
+    sys.modules['mmdet3d.ops.furthest_point_sample.furthest_point_sample_ext'] = shims.furthest_point_sample_ext
+                                                                                # furthest_point_sample.py:4, 32-33, 67-68
 
 Each namespace has exactly the functions, argument orders and in / out conventions of the module it stands for (outputs
 the reference pre-allocates are written in place).  Everything runs on the GPU through the C ABI of libsst_amd.so
@@ -22,6 +24,7 @@ import torch
 
 from . import _lib
 from . import box_ops as _box
+from . import fps as _fps
 from . import kernels as K
 from . import spconv as _spconv
 from . import voxel as _voxel
@@ -210,6 +213,29 @@ roiaware_pool3d_ext = types.SimpleNamespace(
     points_in_boxes_batch=lambda boxes, pts, out: _box._points_in_boxes_into(boxes, pts, out, _box.PIB_MEMBERSHIP),
     points_in_boxes_cpu=_not_ported('points_in_boxes_cpu'), forward=_not_ported('forward'),
     backward=_not_ported('backward'))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# mmdet3d/ops/furthest_point_sample/furthest_point_sample_ext  (src/furthest_point_sample.cpp: both wrappers take
+# (B, N, m, input, temp, idx) and write idx, the caller's int32 [B, m])
+# ------------------------------------------------------------------------------------------------------------------
+def _fps_wrapper(b, n, m, points_tensor, temp_tensor, idx_tensor):
+    if points_tensor.dim() != 3 or tuple(points_tensor.shape[:2]) != (b, n):
+        raise RuntimeError(f'furthest_point_sampling_wrapper: points of shape {tuple(points_tensor.shape)} for B = {b}, N = {n}')
+    _fps._fps_into(points_tensor, m, temp_tensor, idx_tensor, 'furthest_point_sampling_wrapper')
+    return 1
+
+
+def _fps_with_dist_wrapper(b, n, m, points_tensor, temp_tensor, idx_tensor):
+    if points_tensor.dim() != 3 or tuple(points_tensor.shape) != (b, n, n):
+        raise RuntimeError(f'furthest_point_sampling_with_dist_wrapper: distances of shape {tuple(points_tensor.shape)} for '
+                           f'B = {b}, N = {n}')
+    _fps._fps_with_dist_into(points_tensor, m, temp_tensor, idx_tensor, 'furthest_point_sampling_with_dist_wrapper')
+    return 1
+
+
+furthest_point_sample_ext = types.SimpleNamespace(furthest_point_sampling_wrapper=_fps_wrapper,
+                                                  furthest_point_sampling_with_dist_wrapper=_fps_with_dist_wrapper)
 
 
 # ------------------------------------------------------------------------------------------------------------------
