@@ -546,9 +546,10 @@ typedef struct sst_wgrad_problem_f32 {
   float* dw;
   float* db;
   int32_t out, in;
-  /* optional (both NULL or both set; exact-split group only, in == 128): the X operand is x + x_add_rows[x_add_index[token]] -
-   * rows fp32 [P][in], index int32 [m]: the weight gradient of q | k = (feat + pos) W (sst_basic_block_v2.py:56-60) without
-   * "feat + pos" in memory */
+  /* optional (both NULL or both set; exact-split group only, in a multiple of 128 as for every problem of that group): the X
+   * operand is x + x_add_rows[x_add_index[token]] - rows fp32 [P][in] contiguous (row stride in) and 16-byte aligned, index
+   * int32 [m] with values in [0, P): the weight gradient of q | k = (feat + pos) W (sst_basic_block_v2.py:56-60) without
+   * "feat + pos" in memory.  sst_weight_grad_group_f32 returns SST_ERR_UNSUPPORTED when they are set. */
   const float* x_add_rows;
   const int32_t* x_add_index;
 } sst_wgrad_problem_f32;

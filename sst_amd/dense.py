@@ -71,13 +71,25 @@ def weight_bias_grad(dy, x, want_bias, out_w=None, out_b=None):
     return dw, db
 
 
+def _xadd_on_load_ok(x, xadd):
+    """(rows, index) as wgrad_x6_k reads them: fp32 [P, in] and int32 [m] device tensors, contiguous, the table 16-byte aligned"""
+    rows, index = xadd
+    return (rows.dtype == torch.float32 and rows.dim() == 2 and rows.size(1) == x.size(1) and rows.is_contiguous()
+            and rows.is_cuda and rows.data_ptr() % 16 == 0 and index.dtype == torch.int32 and index.dim() == 1
+            and index.numel() == x.size(0) and index.is_contiguous() and index.is_cuda)
+
+
 def weight_bias_grad_group(problems):
     """Weight / bias gradients of several linears at once: problems = [(dy, x, out_w, out_b | None[, (rows, index)]), ...] with
     contiguous fp32 destinations; the split-K kernels of csrc/wgrad.hip one after the other and ONE reduction launch for all of
     them (sst_weight_grad_group_f32).  The optional fifth element: the X operand is x + rows[index] (the positional rows of an
-    encoder layer), added on load - exact-split group only; elsewhere the sum is formed first.  Problems the kernel is not built
-    for go through weight_bias_grad one by one."""
+    encoder layer), added on load - exact-split group only, and only for what that kernel reads (_xadd_on_load_ok: fp32 table of
+    x's width, int32 index, both contiguous); elsewhere the sum is formed first.  Problems the kernel is not built for go through
+    weight_bias_grad one by one."""
     problems = [tuple(p) + (None,) * (5 - len(p)) for p in problems]
+    # the kernel takes the table and the index as raw pointers: anything it would misread is added here, as a tensor
+    problems = [(dy, x, ow, ob, xadd) if xadd is None or _xadd_on_load_ok(x, xadd) else
+                (dy, x + xadd[0].index_select(0, xadd[1].long()), ow, ob, None) for dy, x, ow, ob, xadd in problems]
     ok = all(dy.stride(1) == 1 and x.stride(1) == 1 and dy.size(0) >= 4096 and dy.size(1) <= 4096 and x.size(1) <= 4096
              and dy.dtype == torch.float32 and x.dtype == torch.float32 and dy.is_cuda and ow.is_contiguous()
              and (ob is None or ob.is_contiguous()) for dy, x, ow, ob, _ in problems)
