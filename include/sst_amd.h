@@ -1232,6 +1232,46 @@ int sst_ssg_assign_f32(const float* d_points, int64_t ld, int64_t n_points, cons
                        float radius, int32_t* d_cluster_id, int32_t* d_n_clusters, int32_t* d_status, void* d_workspace,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The fused SIR stage (csrc/sir_stage.hip): one stage of FSD's SIRLayer - Linear without bias, LayerNorm, activation and the
+ * max pooling over the points of a cluster - in one launch forward and one backward.  Replaces, per stage of
+ * voxel_encoders/voxel_encoder.py:738-750 (layer: voxel_encoders/utils.py:147-189; stack: backbones/sir.py:67-88; pooling:
+ * torch_scatter.scatter_max through ops/sst/sst_ops.py:172-177), a GEMM, sst_add_layernorm_act_fwd_f32,
+ * sst_segment_reduce_long_f32 and sst_concat_gather_f32.  fp32, c == 128, 1 <= k <= 256, deterministic, no float atomics.
+ *   Forward, for every row r of d_x [n, k] (contiguous; rows need not be 16-byte aligned) with group g = d_inverse[r]:
+ *     d_pre[r]   = d_x[r] . d_weight^T (+ d_add_rows[g])    d_weight [128, k] with row stride ldw >= k (a column slice of a
+ *                  wider matrix is passed as it lies); the product is exact fp32 (v_mfma_f32_16x16x4_f32)
+ *     d_y[r]     = act(LayerNorm(d_pre[r]; d_gamma, d_beta, eps)),  act: 0 none, 1 GELU (erf form), 2 ReLU
+ *     d_stats[r] = (mean, rstd), the layout of sst_add_layernorm_act_fwd_f32
+ *     d_pooled[g], d_argmax[g] = max over the group's rows of d_y and the SMALLEST row index attaining it, per column.
+ *   d_add_rows (optional, [m, 128]): the split-weight form of the second stage, whose input the reference builds as
+ *   cat([point_feats, pooled[unq_inv]]) (voxel_encoder.py:744-747): x W^T = point_feats W[:, :128]^T +
+ *   (pooled W[:, 128:]^T)[unq_inv], so the [n, 256] matrix is never formed; the caller computes the small second product.
+ *   The grouping is the CSR of a sorted-unique (d_perm [n], d_inverse [n], d_offsets [m + 1], as sst_segment_reduce_long_f32
+ *   takes them); groups without rows are NOT written.  d_scratch: sst_segment_long_scratch_bytes(n, m, 128) bytes, 256-byte
+ *   aligned, its first 4 m bytes ZEROED ONCE by the caller; the kernel leaves them zeroed.  d_pre, d_y, d_pooled, d_argmax,
+ *   d_add_rows, d_gamma and d_beta must be 16-byte aligned.  NaN / Inf inputs are outside the contract.
+ *   sst_sir_stage_tile_rows(): sorted positions per workgroup (a group crossing a multiple of it is merged across workgroups).
+ *   Backward: d_dpre = gradient of d_pre given d_dy (at d_y, [n, 128]) and d_dpooled (at d_pooled, [m, 128]), either of which
+ *   may be NULL: dy_total[r, c] = dy[r, c] + (argmax[inverse[r], c] == r ? dpooled[inverse[r], c] : 0) is formed on load and
+ *   goes through the row arithmetic of sst_add_layernorm_act_bwd_f32; d_dgamma / d_dbeta [128] are overwritten.  d_workspace:
+ *   sst_sir_gather_segmax_bwd_workspace_bytes(n) bytes.  The gradients of x, W and d_add_rows are products / a segmented sum
+ *   of d_dpre and stay with the caller.
+ *   Errors (nothing is launched): SST_ERR_UNSUPPORTED for c != 128, k outside 1..256 or an unknown act; SST_ERR_ARG for a
+ *   NULL required pointer, a misaligned operand or ldw < k.
+ * ---------------------------------------------------------------------------------------------- */
+int sst_sir_stage_tile_rows(void);
+int sst_sir_gather_segmax_fwd_f32(const float* d_x, int64_t n, int k, const float* d_weight, int64_t ldw, int c,
+                                  const float* d_add_rows, const float* d_gamma, const float* d_beta, float eps, int act,
+                                  const uint32_t* d_perm, const int32_t* d_inverse, const int32_t* d_offsets, int64_t m,
+                                  void* d_scratch, float* d_pre, float* d_stats, float* d_y, float* d_pooled, int32_t* d_argmax,
+                                  void* stream);
+int64_t sst_sir_gather_segmax_bwd_workspace_bytes(int64_t n);
+int sst_sir_gather_segmax_bwd_f32(const float* d_dy, const float* d_dpooled, const int32_t* d_argmax, const int32_t* d_inverse,
+                                  const float* d_pre, const float* d_stats, const float* d_gamma, const float* d_beta, int act,
+                                  int64_t n, int c, int64_t m, float* d_dpre, float* d_dgamma, float* d_dbeta, void* d_workspace,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

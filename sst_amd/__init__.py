@@ -16,6 +16,7 @@ from .sst_ops import (build_mlp, flat2window, flat2window_v2, get_activation, ge
                       get_flat2win_inds, get_flat2win_inds_v2, get_inner_win_inds, get_window_coors,
                       make_continuous_inds, scatter_v2, window2flat, window2flat_v2)
 from .voxel_encoder import DynamicScatterVFE, DynamicVFE, DynamicVFELayer, DynamicVFELayerV2, SIRLayer
+from .sir_stage import enable_fused_sir, sir_stage, sir_stage_ok, sir_stage_tile_rows
 from .sst_input_layer import PseudoMiddleEncoderForSpconvFSD, SSTInputLayer, SSTInputLayerV2
 from .sst_basic_block import BasicShiftBlockV2, EncoderLayer, WindowAttention
 from .backbones import SIR, SSTv1, SSTv2
@@ -61,5 +62,5 @@ __all__ = [
     'box_ops', 'boxes_iou_bev', 'boxes_overlap_bev', 'boxes_overlap_1to1', 'nms_gpu', 'nms_normal_gpu',
     'points_in_boxes_gpu', 'points_in_boxes_batch', 'boxes3d_overlaps_lidar', 'box3d_multiclass_nms',
     'furthest_point_sample', 'furthest_point_sample_with_dist', 'fps_segmented', 'ssg_assign', 'ssg', 'ssg_single_sample',
-    'SSGAssigner', 'HybridAssigner',
+    'SSGAssigner', 'HybridAssigner', 'sir_stage', 'sir_stage_ok', 'sir_stage_tile_rows', 'enable_fused_sir',
 ]

@@ -328,6 +328,11 @@ _SIGNATURES = {
     'sst_bn_act_res_bwd_apply_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i64, c_i64, c_i64, c_ptr, c_ptr,
                                              c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float, c_i32, c_ptr, c_i64, c_ptr,
                                              c_i64, c_ptr]),
+    'sst_sir_stage_tile_rows': (c_i32, []),
+    'sst_sir_gather_segmax_fwd_f32': (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_f32, c_i32, c_ptr,
+                                              c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_sir_gather_segmax_bwd_workspace_bytes': (c_i64, [c_i64]),
+    'sst_sir_gather_segmax_bwd_f32': (c_i32, [c_ptr] * 8 + [c_i32, c_i64, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

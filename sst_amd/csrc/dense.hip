@@ -4,43 +4,9 @@
 // All HBM-bound: 1 read + 1 write of 4C B/token forward (+ the residual read), row = one 32-lane group.
 #include <math.h>
 #include "common.h"
+#include "ln_rows.h"
 
 namespace {
-
-constexpr int kLnThreads = 256;
-constexpr int kLnRowsPerBlock = kLnThreads / 32;  // one row per 32-lane half-wave
-constexpr int kLnMaxVec = 4;                      // up to 4 float4 per lane -> C <= 512
-
-// activation folded into the LayerNorm passes ("Linear -> LN -> GELU" of FSD's SIR layers, voxel_encoder.py:628-650):
-// 0 none, 1 GELU (erf form; Abramowitz-Stegun 7.1.26, |error| < 1.5e-7, as in csrc/dense_f32.hip), 2 ReLU
-__device__ __forceinline__ float ln_erf(float z, float& e) {
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.f));
-  e = __expf(-az * az);
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  return copysignf(fmaf(-poly, e, 1.f), z);
-}
-__device__ __forceinline__ float ln_act(float x, int act) {
-  if (act == 1) {
-    float e;
-    return 0.5f * x * (1.f + ln_erf(x * 0.70710678118654752f, e));
-  }
-  return act == 2 ? fmaxf(x, 0.f) : x;
-}
-__device__ __forceinline__ float ln_act_grad(float x, int act) {
-  if (act == 1) {
-    float e;
-    const float phi = 0.5f * (1.f + ln_erf(x * 0.70710678118654752f, e));
-    return fmaf(x * 0.3989422804014327f, e, phi);
-  }
-  return act == 2 ? (x > 0.f ? 1.f : 0.f) : 1.f;
-}
-
-__device__ __forceinline__ float group32_sum(float v) {
-#pragma unroll
-  for (int d = 1; d < 32; d <<= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 // y = LN(x + r) * w + b ; stats[row] = (mean, rstd).  r may be null.
 __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_k(const float* __restrict__ x, const float* __restrict__ r,
@@ -80,8 +46,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_k(const float* __restri
     for (int k = 0; k < kLnMaxVec; ++k) {
       const int col = k * 128 + lane * 4;
       if (k < nvec && col < c) {
-        const float dx = v[k].x - mean, dy = v[k].y - mean, dz = v[k].z - mean, dw = v[k].w - mean;
-        q += dx * dx + dy * dy + dz * dz + dw * dw;
+        q += ln_sqdev4(v[k], mean);
       }
     }
     const float var = group32_sum(q) / (float)c;
@@ -92,12 +57,7 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_k(const float* __restri
       if (k < nvec && col < c) {
         const float4 wv = *(const float4*)(w + col);
         const float4 bv = *(const float4*)(b + col);
-        float4 o;
-        o.x = (v[k].x - mean) * rstd * wv.x + bv.x;
-        o.y = (v[k].y - mean) * rstd * wv.y + bv.y;
-        o.z = (v[k].z - mean) * rstd * wv.z + bv.z;
-        o.w = (v[k].w - mean) * rstd * wv.w + bv.w;
-        if (act) o.x = ln_act(o.x, act), o.y = ln_act(o.y, act), o.z = ln_act(o.z, act), o.w = ln_act(o.w, act);
+        const float4 o = ln_norm_act4(v[k], mean, rstd, wv, bv, act);
         *(float4*)(y + row * c + col) = o;
         if (y_plus_pos != nullptr) {   // the next encoder layer's q / k input: y + positional embedding (row of a small table)
           const float4 pv = *(const float4*)(pos_table + (size_t)pos_idx[row] * c + col);
@@ -107,91 +67,6 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_fwd_k(const float* __restri
     }
     if (lane == 0) stats[row] = make_float2(mean, rstd);
   }
-}
-
-// Given s = x + r (saved), stats, dy:  dx = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * w
-// dw += sum_rows dy * xhat ; db += sum_rows dy   (block partials in LDS, then one atomic per column per block)
-__global__ __launch_bounds__(kLnThreads) void add_ln_bwd_k(const float* __restrict__ dy, const float* __restrict__ s,
-                                                           const float2* __restrict__ stats,
-                                                           const float* __restrict__ w,
-                                                           const float* __restrict__ b, int act, int64_t m, int c,
-                                                           float* __restrict__ dx,
-                                                           float* __restrict__ partials) {
-  extern __shared__ __attribute__((aligned(16))) float part[];  // [2][c]
-  for (int i = threadIdx.x; i < 2 * c; i += kLnThreads) part[i] = 0.f;
-  __syncthreads();
-  const int lane = threadIdx.x & 31;
-  const int sub = threadIdx.x >> 5;
-  const int nvec = (c + 127) / 128;
-  float4 aw[kLnMaxVec], ab[kLnMaxVec];
-#pragma unroll
-  for (int k = 0; k < kLnMaxVec; ++k) aw[k] = ab[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int64_t row = (int64_t)blockIdx.x * kLnRowsPerBlock + sub; row < m; row += (int64_t)gridDim.x * kLnRowsPerBlock) {
-    const float2 st = stats[row];
-    float4 g[kLnMaxVec], xh[kLnMaxVec];
-    float sg = 0.f, sgx = 0.f;
-#pragma unroll
-    for (int k = 0; k < kLnMaxVec; ++k) {
-      const int col = k * 128 + lane * 4;
-      g[k] = xh[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (k < nvec && col < c) {
-        float4 d = *(const float4*)(dy + row * c + col);
-        const float4 sv = *(const float4*)(s + row * c + col);
-        const float4 wv = *(const float4*)(w + col);
-        xh[k] = make_float4((sv.x - st.x) * st.y, (sv.y - st.x) * st.y, (sv.z - st.x) * st.y, (sv.w - st.x) * st.y);
-        if (act) {   // the gradient arrives behind the activation: through it first, at the recomputed LayerNorm output
-          const float4 bv = *(const float4*)(b + col);
-          d.x *= ln_act_grad(fmaf(xh[k].x, wv.x, bv.x), act);
-          d.y *= ln_act_grad(fmaf(xh[k].y, wv.y, bv.y), act);
-          d.z *= ln_act_grad(fmaf(xh[k].z, wv.z, bv.z), act);
-          d.w *= ln_act_grad(fmaf(xh[k].w, wv.w, bv.w), act);
-        }
-        g[k] = make_float4(d.x * wv.x, d.y * wv.y, d.z * wv.z, d.w * wv.w);
-        sg += g[k].x + g[k].y + g[k].z + g[k].w;
-        sgx += g[k].x * xh[k].x + g[k].y * xh[k].y + g[k].z * xh[k].z + g[k].w * xh[k].w;
-        aw[k].x += d.x * xh[k].x;
-        aw[k].y += d.y * xh[k].y;
-        aw[k].z += d.z * xh[k].z;
-        aw[k].w += d.w * xh[k].w;
-        ab[k].x += d.x;
-        ab[k].y += d.y;
-        ab[k].z += d.z;
-        ab[k].w += d.w;
-      }
-    }
-    const float mg = group32_sum(sg) / (float)c;
-    const float mgx = group32_sum(sgx) / (float)c;
-#pragma unroll
-    for (int k = 0; k < kLnMaxVec; ++k) {
-      const int col = k * 128 + lane * 4;
-      if (k < nvec && col < c) {
-        float4 o;
-        o.x = st.y * (g[k].x - mg - xh[k].x * mgx);
-        o.y = st.y * (g[k].y - mg - xh[k].y * mgx);
-        o.z = st.y * (g[k].z - mg - xh[k].z * mgx);
-        o.w = st.y * (g[k].w - mg - xh[k].w * mgx);
-        *(float4*)(dx + row * c + col) = o;
-      }
-    }
-  }
-  // the row groups of the block add their column sums one after the other (a float atomicAdd into LDS made the order - and
-  // the last bits of d(gamma), d(beta) - depend on the schedule)
-  for (int turn = 0; turn < kLnRowsPerBlock; ++turn) {
-    if (sub == turn) {
-#pragma unroll
-      for (int k = 0; k < kLnMaxVec; ++k) {
-        const int col = k * 128 + lane * 4;
-        if (k < nvec && col < c) {
-          part[col + 0] += aw[k].x, part[col + 1] += aw[k].y, part[col + 2] += aw[k].z, part[col + 3] += aw[k].w;
-          part[c + col + 0] += ab[k].x, part[c + col + 1] += ab[k].y, part[c + col + 2] += ab[k].z, part[c + col + 3] += ab[k].w;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  // block partials [gridDim.x][2c]; reduced by colsum_partials_k (no global atomics, deterministic)
-  float* dst = partials + (int64_t)blockIdx.x * 2 * c;
-  for (int i = threadIdx.x; i < 2 * c; i += kLnThreads) dst[i] = part[i];
 }
 
 // Any width 1 <= C <= 512 (FSD's first SIR layer of a stack and its relative-position gate have C = 5 + point features: 133,
@@ -366,29 +241,6 @@ __global__ __launch_bounds__(kLnThreads) void add_ln_bwd_c128_k(const float* __r
   }
   float* dst = partials + (int64_t)blockIdx.x * 2 * C;
   for (int i = threadIdx.x; i < 2 * C; i += kLnThreads) dst[i] = part[i];
-}
-
-// out[i] = sum_b partials[b][i], i < width.  Block = 32 columns x 32 slices of the nb partial rows.
-__global__ __launch_bounds__(1024) void colsum_partials_k(const float* __restrict__ partials, int nb, int width,
-                                                          float* __restrict__ out0, float* __restrict__ out1,
-                                                          int split) {
-  __shared__ float red[32][33];
-  const int cx = threadIdx.x & 31, gy = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + cx;
-  float acc = 0.f;
-  if (i < width)
-    for (int b = gy; b < nb; b += 32) acc += partials[(int64_t)b * width + i];
-  red[gy][cx] = acc;
-  __syncthreads();
-  if (gy == 0 && i < width) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) t += red[k][cx];
-    if (i < split)
-      out0[i] = t;
-    else
-      out1[i - split] = t;
-  }
 }
 
 // out[col] += sum over rows of x[row, col]; out must be zero on entry.  c % 4 == 0, c <= 1024.
@@ -761,7 +613,7 @@ static int add_layernorm_bwd_any(const float* d_dy, const float* d_dy2, const fl
     hipLaunchKernelGGL(add_ln_bwd_c128_k, dim3(grid), dim3(kLnThreads), 0, st, d_dy, d_dy2, d_sum, (const float2*)d_stats,
                        d_weight, m, d_dx, partials);
   else
-    hipLaunchKernelGGL(add_ln_bwd_k, dim3(grid), dim3(kLnThreads), 2 * c * sizeof(float), st, d_dy, d_sum,
+    hipLaunchKernelGGL(add_ln_bwd_k<false>, dim3(grid), dim3(kLnThreads), 2 * c * sizeof(float), st, d_dy, d_sum,
                        (const float2*)d_stats, d_weight, d_bias, act, m, c, d_dx, partials);
   if (partial_rows != nullptr)     // the caller finishes the column sums itself (a rider on its next reduction launch)
     *partial_rows = grid;

@@ -97,7 +97,7 @@ def sort_pairs_u64(keys, key_bits):
 class UniquePlan(object):
     """Result of unique_rows: the grouping of N rows into M sorted-unique rows (all device int32)."""
     __slots__ = ('n', 'm', 'num', 'perm', 'inverse', 'offsets', 'ukeys', 'mins', 'extents', 'ncols', 'has_invalid_group',
-                 'scratch')
+                 'scratch', 'native')   # native: set by unique_rows itself - every group then has at least one row
 
     def counts(self):
         return self.offsets[1:self.m + 1] - self.offsets[:self.m]
@@ -130,6 +130,7 @@ def unique_rows(coors, mins=None, extents=None, invalid_if_negative=False, defer
         extents = [1] * k
     plan = UniquePlan()
     plan.n, plan.ncols = n, k
+    plan.native = True
     plan.mins, plan.extents = list(mins), list(extents)
     plan.perm = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     plan.inverse = torch.empty(max(n, 1), dtype=torch.int32, device=dev)

@@ -28,6 +28,7 @@ from . import kernels as K
 from .dense import add_layer_norm, tall_linear
 from .norm import batch_norm_act, build_norm_layer
 from .registry import VOXEL_ENCODERS
+from .sir_stage import sir_stage, sir_stage_ok
 from .sst_ops import build_mlp, get_activation_layer, plan_of_inverse, unique_with_plan
 from .vfe_fused import UniquePlanAdapter, fused_vfe2, fused_vfe2_ok
 from .voxel import DynamicScatter, build_scatter_plan
@@ -313,9 +314,39 @@ class SIRLayer(_PointGroupEncoder):
             DynamicVFELayer(cin, cout, norm_cfg) if plain else DynamicVFELayerV2(cin, cout, norm_cfg, act=act, dropout=dropout)
             for cin, cout in self._layer_widths(feat_channels)])
         self.num_vfe = len(self.vfe_layers)
+        # True: a stage that sir_stage_ok accepts runs as the fused stage kernel (sir_stage.py).  Off by default: its product
+        # rounds differently from the library GEMM of the layer-by-layer path (sst_amd.enable_fused_sir switches a whole model)
+        self.fused_stage = False
 
     def map_voxel_center_to_point(self, voxel_mean, voxel2point_inds):
         return voxel_mean[voxel2point_inds]
+
+    def _encode(self, x, grouping, mode):
+        if not self.fused_stage:
+            return super()._encode(x, grouping, mode)
+        # stage by stage: the fused kernel where it applies, today's modules where it does not.  A fused later stage takes the
+        # previous stage's pooled rows through the second half of its weight instead of cat([x, pooled[index]])
+        pooled, plan = [], grouping.plan
+        for li, layer in enumerate(self.vfe_layers):
+            act = getattr(layer, 'act', 'relu')      # DynamicVFELayer has a fixed ReLU and no dropout
+            dropout = getattr(layer, 'dropout', None)
+            weight = layer.linear.weight
+            if li == 0:
+                if sir_stage_ok(x, layer.linear, layer.norm, act, dropout, mode, plan):
+                    x, p = sir_stage(x, weight, layer.norm, act, plan)
+                else:
+                    x = layer(x)
+                    p = grouping.reduce(x, mode)
+            else:
+                prev = pooled[-1]
+                c = x.size(1)
+                if c == prev.size(1) and sir_stage_ok(x, layer.linear, layer.norm, act, dropout, mode, plan, k_in=2 * c):
+                    x, p = sir_stage(x, weight[:, :c], layer.norm, act, plan, add_rows=tall_linear(prev, weight[:, c:]))
+                else:
+                    x = layer(K.concat_gather(x, prev, grouping.index, grouping.group_sum))
+                    p = grouping.reduce(x, mode)
+            pooled.append(p)
+        return x, pooled
 
     def forward(self, features, coors, f_cluster=None, points=None, img_feats=None, img_metas=None, return_inv=False,
                 return_both=False, unq_inv_once=None, new_coors_once=None):
