@@ -1272,6 +1272,67 @@ int sst_sir_gather_segmax_bwd_f32(const float* d_dy, const float* d_dpooled, con
                                   int64_t n, int c, int64_t m, float* d_dpre, float* d_dgamma, float* d_dbeta, void* d_workspace,
                                   void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training side of VoteSegHead (csrc/seg_loss.hip): point targets of a batch, the decode / vote losses with the logged
+ * statistics, and their backward.  fp32 data, everything on `stream`, no float atomics, no host read-back, bit-reproducible.
+ * Replaces VoteSegHead.get_targets / get_point_labels / get_vote_target / encode_vote_targets and losses of
+ * mmdet3d/models/decode_heads/segmentation_head.py:106-275 (and autograd's backward of the latter).
+ *
+ * Targets, one launch for all samples:
+ *   d_points [n, ld >= 3] fp32 (columns 0..2 are read), sample s = rows d_pt_offsets[s] .. d_pt_offsets[s + 1] (device int32
+ *   [batch + 1]); d_boxes [n_boxes, 7] fp32 (x, y, z_bottom, w, l, h, rz) of all samples, d_box_labels int64 [n_boxes], sample
+ *   s = boxes d_box_offsets[s] .. d_box_offsets[s + 1].  A point belongs to the FIRST box of its own sample with label >= 0
+ *   that holds it (dpp_box / dpp_classify of csrc/pib_test.h != 0) with w and l enlarged by (float)(2.0 * extra_width) when
+ *   has_extra_width (enlarged_box_hw, lidar_box3d.py:331-346: for a negative width a box whose enlarged w or l would be <= 0
+ *   keeps its own extents); boxes with label < 0 are skipped.  Outputs, every element written: d_inbox int32 [n] (index into
+ *   d_boxes or -1), d_labels int64 [n] (the box's label or bg_label), d_vote_mask uint8 [n] (inbox >= 0), d_vote_targets
+ *   [n, 3] = sign(delta) * sqrt(|delta|) with delta = centre - point, centre = (x, y, z_bottom + h * 0.5) or
+ *   d_centers[inbox] (optional, [n_boxes, 3]); 0 for background rows.  Every operation is rounded once, the root correctly.
+ *   sst_seg_targets_box_tile(): boxes per LDS tile.
+ *
+ * Losses.  d_logits [n, c], d_vote_preds [n, 3c], d_labels int64 [n], d_vote_targets [n, 3], d_vote_mask uint8 [n],
+ * 1 <= c <= 32, n >= 1.  With z = logit_scale * logit:
+ *   SST_SEG_SIGMOID_FOCAL  t[i, k] = (labels[i] == k) (label c = background: all zero), p = sigmoid(z),
+ *                          e = (max(z, 0) - t z + log1p(exp(-|z|))) * (alpha t + (1 - alpha)(1 - t)) * |t - p|^gamma,
+ *                          loss_sem = sum(e) / (n c)      (py_sigmoid_focal_loss, mmdet3d/models/losses/focal_loss.py:13-67)
+ *   SST_SEG_SOFTMAX_CE     e_i = -w[labels[i]] * log_softmax(z_i)[labels[i]] (w = 1 when d_class_weight is NULL; the last
+ *                          class is the background), loss_sem = sum(e) / n
+ *   vote loss, both modes  over the points with d_vote_mask and 0 <= labels[i] < c:
+ *                          loss_vote = sum_d |vote_preds[i, 3 labels[i] + d] - vote_targets[i, d]| / (3 num_valid), 0 without any
+ *   statistics             d_score_thresh (device, NULL: none).  Sigmoid: c thresholds, tp[k] = #(p[i, k] > thr[k] and
+ *                          labels[i] == k).  Cross entropy: n_groups thresholds and d_class_group int32 [c - 1] (the group of
+ *                          each non-background class, anything else: in no group): group_score[g] = sum of the softmax over
+ *                          the classes of g, pred[g] = group_score[g] > thr[g], num_fg = sum_g #pred[g], tp[k] = #(pred[group
+ *                          of k] and labels[i] == k).  real[k] = #(labels[i] == k), recall = tp / (real + 1e-5).
+ *   d_out float [2 + c + 1]: loss_sem, loss_vote (neither multiplied by a loss weight), recall per class, num_fg.
+ *   d_counts int64 [2 + 2c]: num_valid, status, tp per class, real per class.  status bit 0: a label outside [0, c] (sigmoid)
+ *   or [0, c) (cross entropy) - the row contributes nothing; bit 1: a masked point whose label is no class - no vote term.
+ *   Forward = a launch writing one record per sst_seg_loss_tile_rows() rows into d_workspace
+ *   (sst_seg_loss_workspace_bytes(n, c)) and a one-workgroup launch adding the records in index order; sums are carried in
+ *   fp64 from the lane on.  Backward = one launch: d_g[2] (device: upstream gradient x loss weight of loss_sem, loss_vote)
+ *   and the forward's d_counts -> d_dlogits [n, c] and d_dvote_preds [n, 3c], every element written; recomputed from the
+ *   logits.  The L1 gradient is sign(pred - target) / (3 num_valid), sign(0) = 0.
+ *   Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer, n < 1 or gamma < 0; SST_ERR_UNSUPPORTED for c
+ *   outside 1..32, an unknown mode, or statistics over 32 classes in more than 28 groups (LDS).
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_SEG_SIGMOID_FOCAL 0
+#define SST_SEG_SOFTMAX_CE 1
+int sst_seg_targets_box_tile(void);
+int sst_seg_targets_f32(const float* d_points, int64_t ld, int64_t n, const int32_t* d_pt_offsets, int batch,
+                        const float* d_boxes, const int64_t* d_box_labels, const int32_t* d_box_offsets, int64_t n_boxes,
+                        int has_extra_width, double extra_width, int64_t bg_label, const float* d_centers, int32_t* d_inbox,
+                        int64_t* d_labels, float* d_vote_targets, uint8_t* d_vote_mask, void* stream);
+int sst_seg_loss_tile_rows(void);
+int64_t sst_seg_loss_workspace_bytes(int64_t n, int c);
+int sst_seg_loss_fwd_f32(const float* d_logits, const float* d_vote_preds, const int64_t* d_labels, const float* d_vote_targets,
+                         const uint8_t* d_vote_mask, int64_t n, int c, int mode, float logit_scale, float gamma, float alpha,
+                         const float* d_class_weight, const float* d_score_thresh, const int32_t* d_class_group, int n_groups,
+                         float* d_out, int64_t* d_counts, void* d_workspace, void* stream);
+int sst_seg_loss_bwd_f32(const float* d_logits, const float* d_vote_preds, const int64_t* d_labels, const float* d_vote_targets,
+                         const uint8_t* d_vote_mask, int64_t n, int c, int mode, float logit_scale, float gamma, float alpha,
+                         const float* d_class_weight, const float* d_g, const int64_t* d_counts, float* d_dlogits,
+                         float* d_dvote_preds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

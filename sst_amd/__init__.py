@@ -35,6 +35,8 @@ from .virtual_voxel import VirtualVoxelExtractor  # noqa: F401
 from . import box_ops  # noqa: F401
 from .box_ops import (box3d_multiclass_nms, boxes3d_overlaps_lidar, boxes_iou_bev, boxes_overlap_1to1,  # noqa: F401
                       boxes_overlap_bev, nms_gpu, nms_normal_gpu, points_in_boxes_batch, points_in_boxes_gpu)
+from . import seg_loss  # noqa: F401
+from .seg_loss import seg_point_targets, seg_vote_loss  # noqa: F401
 from . import detectors  # noqa: F401
 from .detectors import (DETECTORS, HEADS, NECKS, FSD, FSDV2, DynamicCenterPoint, DynamicVoxelNet, SingleStageFSD, SingleStageFSDV2, VoteSegHead,  # noqa: F401
                         VoteSegmentor, Voxel2PointScatterNeck, build_detector, build_head, build_model, build_neck,
@@ -63,4 +65,5 @@ __all__ = [
     'points_in_boxes_gpu', 'points_in_boxes_batch', 'boxes3d_overlaps_lidar', 'box3d_multiclass_nms',
     'furthest_point_sample', 'furthest_point_sample_with_dist', 'fps_segmented', 'ssg_assign', 'ssg', 'ssg_single_sample',
     'SSGAssigner', 'HybridAssigner', 'sir_stage', 'sir_stage_ok', 'sir_stage_tile_rows', 'enable_fused_sir',
+    'seg_loss', 'seg_point_targets', 'seg_vote_loss',
 ]

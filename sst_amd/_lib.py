@@ -333,6 +333,15 @@ _SIGNATURES = {
                                               c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_sir_gather_segmax_bwd_workspace_bytes': (c_i64, [c_i64]),
     'sst_sir_gather_segmax_bwd_f32': (c_i32, [c_ptr] * 8 + [c_i32, c_i64, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_seg_targets_box_tile': (c_i32, []),
+    'sst_seg_targets_f32': (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_i32, ctypes.c_double, c_i64,
+                                    c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_seg_loss_tile_rows': (c_i32, []),
+    'sst_seg_loss_workspace_bytes': (c_i64, [c_i64, c_i32]),
+    'sst_seg_loss_fwd_f32': (c_i32, [c_ptr] * 5 + [c_i64, c_i32, c_i32, c_f32, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_i32, c_ptr,
+                                                   c_ptr, c_ptr, c_ptr]),
+    'sst_seg_loss_bwd_f32': (c_i32, [c_ptr] * 5 + [c_i64, c_i32, c_i32, c_f32, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                                   c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -4,14 +4,17 @@ constructs on the way from points to the features the heads consume, with the re
 sub-module names (-> ``state_dict`` keys) and data flow.  Every sub-config whose ``type`` this library implements is BUILT
 (Voxelization, DynamicScatterVFE, PseudoMiddleEncoderForSpconvFSD / SSTInputLayerV2, SimpleSparseUNet / SSTv2,
 Voxel2PointScatterNeck, VoteSegHead, SIR, ClusterAssigner / SSGAssigner / HybridAssigner, the virtual-voxel stage with multiscale_cfg / as_rpn,
-DynamicPointROIExtractor); the rest - box heads, losses, target assignment, box decoding, NMS - is kept as
-its config under ``self.unbuilt`` and never run (the box ops those heads call are in ``sst_amd.box_ops``).  Nothing here computes a loss.
+DynamicPointROIExtractor); the rest - box heads, their losses and target assignment, box decoding, NMS - is kept as
+its config under ``self.unbuilt`` and never run (the box ops those heads call are in ``sst_amd.box_ops``).  The one loss computed
+here is the segmentor's own: VoteSegHead's point targets, decode loss and vote loss (``sst_amd.seg_loss``), which makes
+``VoteSegmentor.forward_train`` a whole training step from points and ground-truth boxes to parameter gradients.
 
 Reference:
   VoteSegmentor            mmdet3d/models/detectors/single_stage_fsd.py:155-384 (__init__, voxelize, extract_feat, reorder,
-                           the prediction part of simple_test)
+                           forward_train :280-342, the prediction part of simple_test)
   Voxel2PointScatterNeck   mmdet3d/models/necks/voxel2point_neck.py:9-62
-  VoteSegHead              mmdet3d/models/decode_heads/segmentation_head.py:16-105, 327-331 (forward, decode_vote_targets)
+  VoteSegHead              mmdet3d/models/decode_heads/segmentation_head.py:16-278 (forward, losses, forward_train,
+                           get_targets, decode_vote_targets)
   SingleStageFSD / FSD     single_stage_fsd.py:389-483 (__init__, extract_feat), two_stage_fsd.py (roi_head: config only)
   SingleStageFSDV2 / FSDV2 single_stage_fsd_v2.py:38-271, 375-433 (the stage itself: sst_amd/virtual_voxel.py),
                            two_stage_fsd_v2.py:11-60
@@ -22,6 +25,7 @@ import torch
 from torch import nn
 
 from . import kernels as K
+from . import seg_loss
 from .cluster import ClusterAssigner, HybridAssigner, SSGAssigner
 from .registry import BACKBONES, MODELS, ROI_EXTRACTORS, Registry, build_backbone, build_middle_encoder, build_voxel_encoder
 from .sst_ops import build_mlp, scatter_v2
@@ -95,9 +99,15 @@ class Voxel2PointScatterNeck(nn.Module):
 
 @HEADS.register_module()
 class VoteSegHead(nn.Module):
-    """per-point class logits and class-wise centre votes (decode_heads/segmentation_head.py:16-105): the forward pass and
-    the vote decoding.  Parameters: ``pre_seg_conv`` (build_mlp), ``conv_seg``, ``voting`` - the reference's names.  Losses
-    and target assignment (points in boxes) are the detector's training side: not here."""
+    """per-point class logits and class-wise centre votes (decode_heads/segmentation_head.py:16-278): the forward pass, the
+    vote decoding, and the training side - point targets (points in ground-truth boxes), the decode loss, the vote loss and the
+    logged recalls, by the kernels of csrc/seg_loss.hip (``sst_amd.seg_loss``).  Parameters: ``pre_seg_conv`` (build_mlp),
+    ``conv_seg``, ``voting`` - the reference's names.
+
+    Built losses: ``loss_decode`` = sigmoid ``FocalLoss`` or softmax ``CrossEntropyLoss`` with mean reduction, ``loss_vote`` =
+    ``L1Loss`` with mean reduction.  The configs are parsed at construction without raising (``loss_mode`` says what was found,
+    ``loss_unbuilt`` why ``losses`` would refuse); anything else - a ``loss_aux`` among it - raises NotImplementedError when
+    ``losses`` is called."""
 
     def __init__(self, in_channel, num_classes, hidden_dims=(), dropout_ratio=0.5, conv_cfg=dict(type='Conv1d'),
                  norm_cfg=dict(type='naiveSyncBN1d'), act_cfg=dict(type='ReLU'), loss_decode=None, loss_vote=None,
@@ -113,8 +123,34 @@ class VoteSegHead(nn.Module):
         self.dropout = nn.Dropout(dropout_ratio) if dropout_ratio > 0 else None
         self.conv_seg = nn.Linear(end_channel, self.num_classes)
         self.voting = nn.Linear(end_channel, self.num_classes * 3)
-        self.loss_cfg = dict(loss_decode=loss_decode, loss_vote=loss_vote, loss_aux=loss_aux)   # not built: out of scope
+        self.loss_cfg = dict(loss_decode=loss_decode, loss_vote=loss_vote, loss_aux=loss_aux)
         self.train_cfg = self.test_cfg = None
+        self.last_counts = None
+        self._parse_losses(loss_decode, loss_vote, loss_aux)
+
+    def _parse_losses(self, loss_decode, loss_vote, loss_aux):
+        """what ``losses`` will run: never raises (every shipped config constructs), records what it cannot run"""
+        # the reference's defaults: CrossEntropyLoss without sigmoid (segmentation_head.py:26-30), L1Loss (:31-33)
+        dec = dict(loss_decode) if loss_decode is not None else dict(type='CrossEntropyLoss', use_sigmoid=False)
+        vote = dict(loss_vote) if loss_vote is not None else dict(type='L1Loss')
+        self.loss_mode, self.loss_unbuilt = None, []
+        self.loss_args = dict(gamma=2.0, alpha=0.25, class_weight=None, loss_weight_decode=float(dec.get('loss_weight', 1.0)),
+                              loss_weight_vote=float(vote.get('loss_weight', 1.0)))
+        plain = dec.get('reduction', 'mean') == 'mean'
+        if dec.get('type') == 'FocalLoss' and dec.get('use_sigmoid', True) and plain and \
+                isinstance(dec.get('alpha', 0.25), (int, float)):
+            self.loss_mode = 'sigmoid_focal'
+            self.loss_args.update(gamma=float(dec.get('gamma', 2.0)), alpha=float(dec.get('alpha', 0.25)))
+        elif dec.get('type') == 'CrossEntropyLoss' and not dec.get('use_sigmoid', False) and not dec.get('use_mask', False) \
+                and plain:
+            self.loss_mode = 'softmax_ce'
+            self.loss_args.update(class_weight=dec.get('class_weight', None))
+        else:
+            self.loss_unbuilt.append(f'loss_decode {dec}: only sigmoid FocalLoss and softmax CrossEntropyLoss (mean) are built')
+        if not (vote.get('type') == 'L1Loss' and vote.get('reduction', 'mean') == 'mean'):
+            self.loss_unbuilt.append(f'loss_vote {vote}: only L1Loss (mean) is built')
+        if loss_aux is not None:
+            self.loss_unbuilt.append(f'loss_aux {dict(loss_aux)} is not built')
 
     def forward(self, voxel_feat):
         x = voxel_feat if self.pre_seg_conv is None else self.pre_seg_conv(voxel_feat)
@@ -127,16 +163,78 @@ class VoteSegHead(nn.Module):
     def decode_vote_targets(preds):
         return preds * preds.abs()
 
-    def losses(self, *args, **kwargs):
-        raise NotImplementedError('losses / target assignment are outside the hot path (SURVEY.md section 8)')
+    @staticmethod
+    def encode_vote_targets(delta):
+        return torch.sign(delta) * (delta.abs() ** 0.5)
 
-    forward_train = get_targets = losses
+    def get_targets(self, points_list, gt_bboxes_list, gt_labels_list):
+        """-> (labels int64 [N], vote_targets [N, 3], vote_mask bool [N]) of the batch (segmentation_head.py:212-275), one
+        launch; ``extra_width`` and ``centroid_offset`` come from ``train_cfg``"""
+        labels, vote_targets, vote_mask, _ = seg_loss.seg_point_targets(
+            points_list, gt_bboxes_list, gt_labels_list, self.bg_label, extra_width=_get(self.train_cfg, 'extra_width', None),
+            centroid_offset=bool(_get(self.train_cfg, 'centroid_offset', False)))
+        return labels, vote_targets, vote_mask
+
+    def _stat_args(self, device):
+        """score thresholds (and, for the softmax head, the group of every class) as cached device vectors"""
+        thr = _get(self.train_cfg, 'score_thresh', None)
+        if thr is None:
+            return None, None, None
+        names = list(_get(self.train_cfg, 'class_names'))
+        if self.use_sigmoid:
+            return K.const_tensor(list(thr), device), None, names[:len(thr)]
+        groups = [list(g) for g in _get(self.train_cfg, 'group_names')]
+        group_of = [-1] * (self.num_classes - 1)
+        for gi, g in enumerate(groups):
+            for name in g:
+                group_of[names.index(name)] = gi
+        return K.const_tensor(list(thr), device), K.const_tensor(group_of, device, torch.int32), names
+
+    def losses(self, seg_logit, vote_preds, seg_label, vote_targets, vote_mask):
+        """the reference's dict (segmentation_head.py:106-173): loss_sem_seg, loss_vote, recall_<name> per class and, for the
+        softmax head, num_fg.  Three launches and no host read; the reference's asserts on the labels are the status word of
+        ``self.last_counts`` (``check_status()``)."""
+        if self.loss_unbuilt:
+            raise NotImplementedError('; '.join(self.loss_unbuilt))
+        thr, group_of, names = self._stat_args(seg_logit.device)
+        loss_sem, loss_vote, recall, num_fg, counts = seg_loss.seg_vote_loss(
+            seg_logit.float().contiguous(), vote_preds.float().contiguous(), seg_label.contiguous(),
+            vote_targets.contiguous(), vote_mask.contiguous(),
+            mode=seg_loss.SIGMOID_FOCAL if self.use_sigmoid else seg_loss.SOFTMAX_CE, logit_scale=self.logit_scale,
+            score_thresh=thr, class_group=group_of, **self.loss_args)
+        self.last_counts = counts
+        loss = dict(loss_sem_seg=loss_sem, loss_vote=loss_vote)
+        if thr is not None:
+            if self.use_sigmoid:
+                for i, name in enumerate(names):
+                    loss[f'recall_{name}'] = recall[i]
+            else:
+                for g in _get(self.train_cfg, 'group_names'):
+                    for name in g:
+                        loss[f'recall_{name}'] = recall[names.index(name)]
+                loss['num_fg'] = num_fg
+        return loss
+
+    def check_status(self):
+        """the reference's asserts on the labels of the last ``losses`` call (segmentation_head.py:124-126, :134-135), for
+        whoever wants them: reads one word back"""
+        assert self.last_counts is not None, 'no losses() call yet'
+        status = int(self.last_counts[1].item())
+        assert not status & seg_loss.STATUS_BAD_LABEL, 'a segmentation label lies outside the classes of this head'
+        assert not status & seg_loss.STATUS_MASKED_NO_CLASS, 'a point with a vote target carries no class label'
+
+    def forward_train(self, inputs, img_metas, pts_semantic_mask, vote_targets, vote_mask, return_preds=False):
+        seg_logits, vote_preds = self.forward(inputs)
+        losses = self.losses(seg_logits, vote_preds, pts_semantic_mask, vote_targets, vote_mask)
+        if return_preds:
+            return losses, dict(seg_logits=seg_logits, vote_preds=vote_preds)
+        return losses
 
 
 @DETECTORS.register_module()
 class VoteSegmentor(nn.Module):
     """points -> dynamic voxelisation -> DynamicScatterVFE -> middle encoder -> sparse backbone -> point features -> class
-    logits + votes (single_stage_fsd.py:155-384 without the loss side)."""
+    logits + votes, and in training the head's losses (single_stage_fsd.py:155-384)."""
 
     def __init__(self, voxel_layer, voxel_encoder, middle_encoder, backbone, segmentation_head, decode_neck=None,
                  auxiliary_head=None, voxel_downsampling_size=None, train_cfg=None, test_cfg=None, init_cfg=None,
@@ -229,6 +327,26 @@ class VoteSegmentor(nn.Module):
                     batch_idx=pts_coors[:, 0], decoder_features=decoder_features)
 
     simple_test = forward
+
+    def forward_train(self, points, img_metas, gt_bboxes_3d, gt_labels_3d, as_subsegmentor=False):
+        """points + ground-truth boxes -> the loss dict (single_stage_fsd.py:280-342); with ``as_subsegmentor`` the output dict
+        of ``forward`` plus ``losses`` - what the FSD detectors run in every training step"""
+        points = self.preprocess(points)
+        labels, vote_targets, vote_mask = self.segmentation_head.get_targets(points, gt_bboxes_3d, gt_labels_3d)
+        res = self.extract_feat(points, img_metas)
+        (feats, valid), pts_coors, batch_points = res[0], res[1], res[2]
+        decoder_features = res[3] if self.use_multiscale_features else None
+        if self._dropped:           # only the SST-based segmentor drops voxels: no compaction otherwise
+            batch_points, pts_coors = batch_points[valid], pts_coors[valid]
+            labels, vote_targets, vote_mask = labels[valid], vote_targets[valid], vote_mask[valid]
+        assert feats.size(0) == labels.size(0)
+        losses, preds = self.segmentation_head.forward_train(feats, img_metas, labels, vote_targets, vote_mask,
+                                                             return_preds=True)
+        if not as_subsegmentor:
+            return losses
+        return dict(seg_points=batch_points, seg_logits=preds['seg_logits'], seg_vote_preds=preds['vote_preds'],
+                    offsets=self.segmentation_head.decode_vote_targets(preds['vote_preds']), seg_feats=feats,
+                    batch_idx=pts_coors[:, 0], losses=losses, decoder_features=decoder_features)
 
 
 @DETECTORS.register_module()
