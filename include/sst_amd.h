@@ -714,6 +714,9 @@ int sst_tall_linear_add_rows_f32x6(const float* d_x, int64_t ldx, const float* d
  * [P][128], index int32 [m].  One launch; "x + pos" is formed in registers. */
 int sst_inproj_pos_f32x6(const float* d_x, int64_t ldx, const float* d_rows, const int32_t* d_index, const float* d_w, int64_t ldw,
                          const float* d_bias, int64_t m, float* d_y, int64_t ldy, void* stream);
+/* The row partition of the sst_tall_linear_*_f32x6 launches for m rows and `groups` column groups (1 - 3): row blocks per group
+ * (8 waves each) and rows per wave (a multiple of 16).  Host arithmetic only. */
+int sst_tall_linear_f32x6_partition(int64_t m, int groups, int64_t* row_blocks, int64_t* rows_per_wave);
 int sst_tall_linear_ln_f32x6(const float* d_x, int64_t ldx, const float* d_w, int64_t ldw, const float* d_bias, int64_t m, int k,
                              const float* d_res, int64_t ldres, const float* d_ln_weight, const float* d_ln_bias, float eps,
                              float* d_y, float* d_sum, float* d_stats, const float* d_pos_table, const int32_t* d_pos_idx,

@@ -115,6 +115,7 @@ _SIGNATURES = {
     'sst_segment_reduce_fwd_f32': (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr,
                                            c_ptr, c_ptr]),
     'sst_encoder_layer_bwd_workspace_bytes': (c_i64, [c_i64, c_i32]),
+    'sst_tall_linear_f32x6_partition': (c_i32, [c_i64, c_i32, c_ptr, c_ptr]),
     'sst_inproj_pos_f32x6': (c_i32, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     'sst_encoder_layer_wpack_bytes': (c_i64, []),
     'sst_encoder_layer_fwd_f32x6': (c_i32, [c_ptr, c_ptr]),

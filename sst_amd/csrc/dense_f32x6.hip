@@ -19,9 +19,10 @@
 //
 // Structure = tall_linear_f32x3_k with THREE bf16 images of W in LDS.  3 x N x K x 2 B is 196 KB for the 256-wide shapes,
 // so the output columns are cut into groups of NW (128 for K = 128, 64 for K = 256: 104 / 101 KB) and a workgroup owns
-// (row block, column group): W of ITS columns resident for the whole kernel, 8 waves, 16-row steps, X fragments straight from
-// global memory (fp32, 2 x 16 bytes per lane and k-step; split into the three packs in registers once per k-step), next
-// tile prefetched, the finished accumulators of a phase written out during the next one.  X is read once per column group;
+// (row block, column group): W of ITS columns resident for the whole kernel, 8 waves, 16-row steps, X read in ROW shape (a
+// lane takes 16 bytes of a row, 8 lanes a 128-byte line) and turned into MFMA fragments through a wave-private 2 KiB LDS block
+// (csrc/tile_io.h), split into the three packs in registers once per k-step, the blocks of the next tile requested as those of
+// this one are used, the finished accumulators of a tile written out during the next one.  X is read once per column group;
 // the groups of one row block are launched `row_blocks` ids apart with row_blocks % 8 == 0, i.e. on the SAME XCD at the
 // same time: the second reader is served by that XCD's L2.
 // A column group may read a different input matrix (`X2` from group `x2_from` on): q | k = (x + pos) W_qk and v = x W_v of
@@ -29,6 +30,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
+#include "tile_io.h"
 
 namespace {
 
@@ -100,10 +102,39 @@ __device__ __forceinline__ int w_lds_row(int n) {  // see csrc/dense_bf16.hip: a
   return 16 * (2 * tp + ((within >> 2) & 1)) + ((within >> 3) << 2) + (within & 3);
 }
 
+// The bias image leaves LDS where the eight 2 KiB transposition blocks (csrc/tile_io.h) do not fit beside it: <384, 64> has
+// 3 x 64 x 384 x 2 = 147 456 B of images, 163 840 - 147 456 = 16 384 B free = exactly 8 x 2 048; its 256 B of bias are then held in
+// registers in the row layout (4 floats per 32-column block and lane: 8 VGPRs).
+template <int K, int NW, int EPI>
+constexpr bool x6_bias_in_regs() {
+  return 3 * NW * K * 2 + NW * (EPI == kEpiAddLN ? 3 : 1) * 4 + 8 * 2048 > 160 * 1024;
+}
+template <int K, int NW, int EPI>
+constexpr int x6_lds_bytes() {
+  return 3 * NW * K * 2 + (x6_bias_in_regs<K, NW, EPI>() ? 0 : NW * (EPI == kEpiAddLN ? 3 : 1) * 4) + 8 * 2048;
+}
+
 // K: contraction width; NW: output columns per workgroup (the whole row when EPI == kEpiAddLN); blockIdx.x = group * row_blocks
 // + row block; `X2` replaces X for the column groups >= x2_from (x2_from >= number of groups: never).
 // XADD: the column groups < x2_from multiply X + xadd_rows[xadd_idx[row]] (rows of width K) instead of X - q | k = (x + positional
 // rows) W_qk and v = x W_v from ONE input tensor: "x + pos" never exists in memory (the table is a few KB and stays in L2)
+//
+// Global access is ROW-shaped (csrc/tile_io.h): every activation-sized stream - X (+ the positional rows, added on the row side),
+// aux_in, the gathered rows, Y, aux_out, ln.yp - is moved with lane l on row l / 8, 16-byte piece l % 8 of a 32-column block, and
+// a block changes between that and the MFMA fragment layout in the wave's 2 KiB of LDS.  The element-wise epilogues run on the
+// row side (same operations per element, so the same bits; aux_in needs no transposition at all); LayerNorm sums a row in the
+// fragment layout as before and only its loads and stores pass through the block.
+// Loads are a ROLLING prefetch through a ring of D blocks (8 VGPRs each): as block s goes to LDS its registers take block s + D -
+// of this tile, or of the NEXT row tile once s + D passes the end - so a request has D k-steps of products to land in.  D = K / 32,
+// a whole tile ahead, for K <= 256; D = 6, half a tile (48 VGPRs, where the fragment-shaped kernel held all 96 without any
+// prefetch), for K = 384; D = 2 under the LayerNorm epilogue, which holds a 128-wide residual as well.  The epilogue operands roll
+// the same way: emit(tp) consumes block tp of the tile being written out and requests block tp of the tile being multiplied.
+// Two places where a request has less cover than that (both on the positional table of the LayerNorm epilogue's second output,
+// a few KB that stay in L2): qr is ONE block, requested a quarter tile before its use, and in a wave's last tile, where nothing
+// is multiplied any more, block tp + 1 is requested in emit(tp) and waited for in emit(tp + 1).
+// After its last tile a wave requests its own first blocks once more, and a wave without rows D blocks of row M - 1 (clamped, in
+// range, never used): every load of the loop is issued on every path, because the compiler's vmcnt for a register only counts
+// requests that are certain to follow - at most D x 512 B per wave of lines that are in L2 already.
 template <int K, int NW, int EPI, bool XADD = false>
 __global__ __launch_bounds__(512, 2) void tall_linear_f32x6_k(
     const float* __restrict__ X, const float* __restrict__ X2, int x2_from, int64_t ldx, const float* __restrict__ W,
@@ -119,50 +150,58 @@ __global__ __launch_bounds__(512, 2) void tall_linear_f32x6_k(
   // SQ_LDS_IDX_ACTIVE in every instantiation (profiles/r06); lane order covers all 64 banks once per group and needs no padding.
   constexpr int KS = K / 32, NTH = 512, TILES = NW / 16, EMITS = TILES / 2;
   constexpr int IMG = NW * K * 2;   // bytes of one bf16 image
+  constexpr bool BIAS_REG = x6_bias_in_regs<K, NW, EPI>();
+  constexpr bool HAS_AUX = EPI == kEpiMulGeluGrad || EPI == kEpiMulReluGrad || EPI == kEpiAdd || EPI == kEpiAddLN || EPI == kEpiAddRows;
+  static_assert(!(BIAS_REG && EPI == kEpiAddLN), "the LayerNorm epilogue reads its row parameters from LDS");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem6[];
   unsigned char* w0 = smem6;
   unsigned char* w1 = smem6 + IMG;
   unsigned char* w2 = smem6 + 2 * IMG;
-  float* bimg = (float*)(smem6 + 3 * IMG);
+  float* bimg = (float*)(smem6 + 3 * IMG);   // absent when BIAS_REG
   auto frag_off = [](int lr, int k8) { return ((lr >> 4) * KS + (k8 >> 5)) * 1024 + (16 * ((k8 >> 3) & 3) + (lr & 15)) * 16; };
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: the row range and every branch on it are uniform
+  const int rr = lane >> 3, rcol = (lane & 7) * 4;   // row side: rows rr and rr + 8 of a tile, columns rcol .. rcol + 3 of a block
+  const tile_xpose io =
+      make_tile_xpose(smem6 + 3 * IMG + (BIAS_REG ? 0 : NW * (EPI == kEpiAddLN ? 3 : 1) * 4) + wv * 2048, lane);
   const int grp = blockIdx.x / row_blocks, rb = blockIdx.x - grp * row_blocks;
   const int nb = grp * NW;   // first output column of this workgroup
   const float* __restrict__ Xg = grp >= x2_from ? X2 : X;
-  const int64_t wave = (int64_t)rb * 8 + (threadIdx.x >> 6);
+  const int64_t wave = (int64_t)rb * 8 + wv;
   int64_t r0 = wave * rows_per_wave;
   const int64_t r1 = r0 + rows_per_wave < M ? r0 + rows_per_wave : M;
-  f32x4 xb[KS][2], xn[KS][2];
-  auto load_x = [&](int64_t r, f32x4 (&dst)[KS][2]) {
-    int64_t row = r + c;
-    row = row < M ? row : M - 1;
-    const float* p = Xg + row * ldx + 8 * g;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      dst[s][0] = *(const f32x4*)(p + 32 * s);
-      dst[s][1] = *(const f32x4*)(p + 32 * s + 4);
-    }
+  // row i (0, 1) of this lane in the tile that starts at r, clamped for loads (a tile past the end reads row M - 1)
+  auto row_of = [&](int64_t r, int i) {
+    const int64_t row = r + 8 * i + rr;
+    return row < M ? row : M - 1;
   };
-  // XADD: the positional rows of the tile in pb / pn (same fragment addresses inside a table row); the row index of the tile
-  // AFTER the one being requested is loaded alongside, so that a table address never waits for its index
+  // row side: a ring of D blocks, block s in slot s % D; D < KS where a whole tile in flight does not fit the registers
+  // (K = 384: half a tile = 6 k-steps x 24 MFMAs, the time a whole K = 128 tile takes; LayerNorm: its epilogue holds a 128-wide
+  // residual as well)
+  constexpr int D = EPI == kEpiAddLN ? 2 : (KS > 8 ? KS / 2 : KS);
+  static_assert(!XADD || D == KS, "the positional rows of a tile are requested with one set of indices");
+  static_assert(KS % D == 0, "a block keeps its slot from tile to tile");
+  f32x4 xr[D][2];
+  auto issue_x = [&](int64_t r, int s) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) xr[s % D][i] = *(const f32x4*)(Xg + row_of(r, i) * ldx + 32 * s + rcol);
+  };
+  // XADD: the positional rows of the same blocks in pr; the row indices of a tile are loaded one tile before its rows are
+  // requested, so that a table address never waits for its index
   const bool xadd = XADD && grp < x2_from;
-  f32x4 pb[XADD ? KS : 1][2], pn[XADD ? KS : 1][2];
-  int32_t pidx = 0;
-  auto load_idx = [&](int64_t r) {
-    int64_t row = r + c;
-    row = row < M ? row : M - 1;
-    pidx = xadd_idx[row];
-  };
-  auto load_p = [&](f32x4 (&dst)[XADD ? KS : 1][2]) {
-    const float* p = xadd_rows + (int64_t)pidx * K + 8 * g;
+  f32x4 pr[XADD ? D : 1][2];
+  int32_t pi[2] = {0, 0};   // indices of the tile whose table rows are requested next
+  auto load_pidx = [&](int64_t r, int32_t (&dst)[2]) {
 #pragma unroll
-    for (int s = 0; s < (XADD ? KS : 1); ++s) {
-      dst[s][0] = *(const f32x4*)(p + 32 * s);
-      dst[s][1] = *(const f32x4*)(p + 32 * s + 4);
-    }
+    for (int i = 0; i < 2; ++i) dst[i] = xadd_idx[row_of(r, i)];
   };
-  load_x(r0 < M ? r0 : M - 1, xb);
-  if (xadd) load_idx(r0 < M ? r0 : M - 1);
+  auto issue_p = [&](int s) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) pr[XADD ? s % D : 0][i] = *(const f32x4*)(xadd_rows + (int64_t)pi[i] * K + 32 * s + rcol);
+  };
+#pragma unroll
+  for (int s = 0; s < D; ++s) issue_x(r0, s);
+  if (xadd) load_pidx(r0, pi);
   // weight fill: W[nb + n][k] (trans_w = 0: row of W; trans_w = 1: W is [K][N], the data gradient of a layer whose parameter is
   // W) -> three bf16 images, row w_lds_row(n).  8 consecutive k per thread and step.
   if (!trans_w) {
@@ -199,45 +238,102 @@ __global__ __launch_bounds__(512, 2) void tall_linear_f32x6_k(
       }
     }
   }
-  for (int n = threadIdx.x; n < NW; n += NTH) {
-    bimg[n] = bias != nullptr ? bias[nb + n] : 0.f;
-    if (EPI == kEpiAddLN) {
-      bimg[NW + n] = ln.w[n];
-      bimg[2 * NW + n] = ln.b[n];
+  f32x4 breg[BIAS_REG ? EMITS : 1];   // BIAS_REG: the bias of this lane's row-side columns
+  if (BIAS_REG) {
+#pragma unroll
+    for (int tp = 0; tp < (BIAS_REG ? EMITS : 1); ++tp)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) breg[tp][e] = bias != nullptr ? bias[nb + 32 * tp + rcol + e] : 0.f;
+  } else {
+    for (int n = threadIdx.x; n < NW; n += NTH) {
+      bimg[n] = bias != nullptr ? bias[nb + n] : 0.f;
+      if (EPI == kEpiAddLN) {
+        bimg[NW + n] = ln.w[n];
+        bimg[2 * NW + n] = ln.b[n];
+      }
     }
   }
   __syncthreads();
   if (r0 >= r1) return;
   if (xadd) {
-    load_p(pb);
-    load_idx(r0 + 16);
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      xb[s][0] += pb[s][0];
-      xb[s][1] += pb[s][1];
-    }
+    for (int s = 0; s < D; ++s) issue_p(s);
+    load_pidx(r0 + 16, pi);
   }
   const int lane_off = lane * 16;
+
+  // epilogue operands, row side: ar[tp] = block tp of aux_in (kEpiAddRows: of the gathered rows) for the tile that is written
+  // out next; qr = the positional rows (ln.yp) of the block that is written out next.  ec / ep: the gather indices
+  // (ln.pos_idx) of the tile being multiplied / being written out, each loaded one tile before it is used.
+  constexpr bool GATHER = EPI == kEpiAddRows || EPI == kEpiAddLN;
+  const bool gather = EPI == kEpiAddRows || (EPI == kEpiAddLN && ln.yp != nullptr);
+  f32x4 ar[HAS_AUX ? EMITS : 1][2], qr[2];
+  int32_t ec[2] = {0, 0}, ep[2] = {0, 0}, en[2] = {0, 0};
+  auto load_eidx = [&](int64_t r, int32_t (&dst)[2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) dst[i] = ln.pos_idx[row_of(r, i)];
+  };
+  auto issue_aux = [&](int64_t r, int tp) {   // rows of the tile at r (kEpiAddRows: the rows ec points at)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int64_t src = EPI == kEpiAddRows ? (int64_t)(ec[i] < 0 ? 0 : ec[i]) : row_of(r, i);
+      ar[HAS_AUX ? tp : 0][i] = *(const f32x4*)(aux_in + src * ldaux + (EPI == kEpiAddLN ? 0 : nb) + 32 * tp + rcol);
+    }
+  };
+  auto issue_q = [&](const int32_t (&idx)[2], int tp) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) qr[i] = *(const f32x4*)(ln.pos_table + (size_t)idx[i] * 128 + 32 * tp + rcol);
+  };
+  if (GATHER && gather) load_eidx(r0, ec);
 
   f32x4 pend[TILES];
   int64_t pend_r0 = 0;
   bool pend_valid = false;
   float ln_rstd = 0.f;
-  auto emit = [&](int tp) {   // 32 finished columns (tiles 2 tp, 2 tp + 1) of the previous row tile; see csrc/dense_f32.hip
-    if (!pend_valid) return;
-    const int64_t row = pend_r0 + c;
-    if (row >= r1) return;
+  // 32 finished columns (tiles 2 tp, 2 tp + 1) of the previous row tile; see csrc/dense_f32.hip.  in_loop: a tile (at r0) is
+  // being multiplied, its operands are requested as those of the finished one are consumed - also while the first tile is
+  // multiplied and nothing is written out yet, which is where the first requests come from.  Every load of the main loop is
+  // issued on every path: the compiler's vmcnt for a register only counts the requests that are certain to follow its own
+  auto request = [&](int tp) {
+    if (EPI == kEpiAddLN) {
+      if (tp == 0) {
+#pragma unroll
+        for (int u = 0; u < EMITS; ++u) issue_aux(r0, u);
+      }
+      if (gather) {
+        if (tp + 1 < EMITS)
+          issue_q(ep, tp + 1);   // (while the first tile is multiplied: rows nobody reads)
+        else
+          issue_q(ec, 0);
+      }
+    } else if (HAS_AUX) {
+      issue_aux(r0, tp);
+    }
+  };
+  auto consume = [&](int tp) {
+    int64_t prow[2];
+    bool pv[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      prow[i] = pend_r0 + 8 * i + rr;
+      pv[i] = prow[i] < M;
+    }
     if (EPI == kEpiAddLN) {
       if (tp == 0) {
         float sum = 0.f;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int n0 = 32 * u + 8 * g;
-          pend[2 * u] += *(const f32x4*)(bimg + n0) + *(const f32x4*)(aux_in + row * ldaux + n0);
-          pend[2 * u + 1] += *(const f32x4*)(bimg + n0 + 4) + *(const f32x4*)(aux_in + row * ldaux + n0 + 4);
+          f32x4 s0, s1;
+          tile_to_frag(io, ar[HAS_AUX ? u : 0][0], ar[HAS_AUX ? u : 0][1], s0, s1);
+          pend[2 * u] += *(const f32x4*)(bimg + n0) + s0;
+          pend[2 * u + 1] += *(const f32x4*)(bimg + n0 + 4) + s1;
           if (aux_out != nullptr) {
-            *(f32x4*)(aux_out + row * ldaux + n0) = pend[2 * u];
-            *(f32x4*)(aux_out + row * ldaux + n0 + 4) = pend[2 * u + 1];
+            f32x4 t[2];
+            tile_to_rows(io, pend[2 * u], pend[2 * u + 1], t[0], t[1]);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+              if (pv[i]) *(f32x4*)(aux_out + prow[i] * ldaux + 32 * u + rcol) = t[i];
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) sum += pend[2 * u][r] + pend[2 * u + 1][r];
@@ -256,71 +352,62 @@ __global__ __launch_bounds__(512, 2) void tall_linear_f32x6_k(
         sq += __shfl_xor(sq, 16, 64);
         sq += __shfl_xor(sq, 32, 64);
         ln_rstd = rsqrtf(sq * (1.f / 128.f) + ln.eps);
-        if (g == 0) ln.stats[row] = make_float2(mean, ln_rstd);
+        if (g == 0 && pend_r0 + c < M) ln.stats[pend_r0 + c] = make_float2(mean, ln_rstd);
       }
       const int n0 = 32 * tp + 8 * g;
       const f32x4 y0 = pend[2 * tp] * ln_rstd * *(const f32x4*)(bimg + NW + n0) + *(const f32x4*)(bimg + 2 * NW + n0);
       const f32x4 y1 =
           pend[2 * tp + 1] * ln_rstd * *(const f32x4*)(bimg + NW + n0 + 4) + *(const f32x4*)(bimg + 2 * NW + n0 + 4);
-      *(f32x4*)(Y + row * ldy + n0) = y0;
-      *(f32x4*)(Y + row * ldy + n0 + 4) = y1;
-      if (ln.yp != nullptr) {
-        const float* prow = ln.pos_table + (size_t)ln.pos_idx[row] * 128 + n0;
-        *(f32x4*)(ln.yp + row * 128 + n0) = y0 + *(const f32x4*)(prow);
-        *(f32x4*)(ln.yp + row * 128 + n0 + 4) = y1 + *(const f32x4*)(prow + 4);
+      f32x4 t[2];
+      tile_to_rows(io, y0, y1, t[0], t[1]);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        if (pv[i]) *(f32x4*)(Y + prow[i] * ldy + 32 * tp + rcol) = t[i];
+      if (gather) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+          if (pv[i]) *(f32x4*)(ln.yp + prow[i] * 128 + 32 * tp + rcol) = t[i] + qr[i];
       }
       return;
     }
-    const int nl = 32 * tp + 8 * g, n0 = nb + nl;
-    const f32x4 b0 = *(const f32x4*)(bimg + nl), b1 = *(const f32x4*)(bimg + nl + 4);
-    f32x4 v0 = pend[2 * tp] + b0, v1 = pend[2 * tp + 1] + b1;
-    if (EPI == kEpiGelu || EPI == kEpiRelu) {
-      if (aux_out != nullptr) {
-        *(f32x4*)(aux_out + row * ldaux + n0) = v0;
-        *(f32x4*)(aux_out + row * ldaux + n0 + 4) = v1;
-      }
+    const int n0 = nb + 32 * tp + rcol;
+    const f32x4 bv = BIAS_REG ? breg[BIAS_REG ? tp : 0] : *(const f32x4*)(bimg + 32 * tp + rcol);
+    f32x4 t[2];
+    tile_to_rows(io, pend[2 * tp], pend[2 * tp + 1], t[0], t[1]);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v0[r] = EPI == kEpiGelu ? gelu_f(v0[r]) : fmaxf(v0[r], 0.f);
-        v1[r] = EPI == kEpiGelu ? gelu_f(v1[r]) : fmaxf(v1[r], 0.f);
-      }
-    }
-    if (EPI == kEpiMulGeluGrad || EPI == kEpiMulReluGrad) {
-      const f32x4 p0 = *(const f32x4*)(aux_in + row * ldaux + n0), p1 = *(const f32x4*)(aux_in + row * ldaux + n0 + 4);
+    for (int i = 0; i < 2; ++i) {
+      f32x4 v = t[i] + bv;
+      if (EPI == kEpiGelu || EPI == kEpiRelu) {
+        if (aux_out != nullptr && pv[i]) *(f32x4*)(aux_out + prow[i] * ldaux + n0) = v;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v0[r] *= EPI == kEpiMulGeluGrad ? gelu_grad_f(p0[r]) : (p0[r] > 0.f ? 1.f : 0.f);
-        v1[r] *= EPI == kEpiMulGeluGrad ? gelu_grad_f(p1[r]) : (p1[r] > 0.f ? 1.f : 0.f);
+        for (int r = 0; r < 4; ++r) v[r] = EPI == kEpiGelu ? gelu_f(v[r]) : fmaxf(v[r], 0.f);
       }
+      if (EPI == kEpiMulGeluGrad || EPI == kEpiMulReluGrad) {
+        const f32x4 p = ar[HAS_AUX ? tp : 0][i];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] *= EPI == kEpiMulGeluGrad ? gelu_grad_f(p[r]) : (p[r] > 0.f ? 1.f : 0.f);
+      }
+      if (EPI == kEpiAdd || EPI == kEpiAddRows) v += ar[HAS_AUX ? tp : 0][i];
+      if (pv[i]) *(f32x4*)(Y + prow[i] * ldy + n0) = v;
     }
-    if (EPI == kEpiAdd) {
-      v0 += *(const f32x4*)(aux_in + row * ldaux + n0);
-      v1 += *(const f32x4*)(aux_in + row * ldaux + n0 + 4);
-    }
-    if (EPI == kEpiAddRows) {
-      const int32_t src = ln.pos_idx[row];
-      const float* arow = aux_in + (int64_t)(src < 0 ? 0 : src) * ldaux + n0;
-      v0 += *(const f32x4*)(arow);
-      v1 += *(const f32x4*)(arow + 4);
-    }
-    *(f32x4*)(Y + row * ldy + n0) = v0;
-    *(f32x4*)(Y + row * ldy + n0 + 4) = v1;
+  };
+  auto emit = [&](int tp, bool in_loop) {
+    if (pend_valid) consume(tp);
+    if (in_loop)
+      request(tp);
+    else if (EPI == kEpiAddLN && gather && tp + 1 < EMITS)
+      issue_q(ep, tp + 1);   // the last tile of the wave: nothing is multiplied meanwhile
   };
 
-  // the next X tile is requested before this one is multiplied while a second tile fits the 256 VGPRs a wave has here (two waves
-  // per SIMD: the three weight images leave LDS for one workgroup per CU): K <= 256 (K = 256: 160 + 64 registers; K = 384 is at 248)
-  constexpr bool PREFETCH = K <= 256;
   for (; r0 < r1; r0 += 16) {
     asm volatile("" ::: "memory");  // W fragments are re-read from LDS per row tile (never hoisted into registers)
-    const bool more = r0 + 16 < r1;
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this tile's X has landed before the next one is requested
-    if (PREFETCH && more) {
-      load_x(r0 + 16, xn);
-      if (xadd) {
-        load_p(pn);          // rows of the index requested one tile ago
-        load_idx(r0 + 32);
-      }
-    }
+    // the tile requested during this one; after the last tile the wave asks for its own rows again (lines it has just read)
+    // instead of branching around the requests
+    const int64_t rn = r0 + 16 < r1 ? r0 + 16 : r0;
+    // the indices of the tiles after this one (rows past the end read row M - 1's); pi: those of the tile at r0 + 16
+    int32_t pj[2] = {0, 0};
+    if (xadd) load_pidx(r0 + 32, pj);
+    if (GATHER && gather) load_eidx(r0 + 16, en);
     f32x4 acc[TILES];
 #pragma unroll
     for (int T = 0; T < TILES; ++T) acc[T] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -333,7 +420,27 @@ __global__ __launch_bounds__(512, 2) void tall_linear_f32x6_k(
 #pragma clang loop unroll(full)
     for (int q = 0; q < G; ++q) {
       const int s = q / QPS, t0 = (q % QPS) * 4;
-      if (q % QPS == 0) split8(xb[s][0], xb[s][1], x0, x1, x2);
+      if (q % QPS == 0) {
+        // block s of this tile: row side (+ its positional rows: the same single fp32 addition) -> fragments -> three packs;
+        // its registers then take block s of the next tile
+        f32x4 a = xr[s % D][0], b = xr[s % D][1];
+        if (XADD && xadd) {
+          a += pr[XADD ? s % D : 0][0];
+          b += pr[XADD ? s % D : 0][1];
+        }
+        f32x4 v0, v1;
+        tile_to_frag(io, a, b, v0, v1);
+        split8(v0, v1, x0, x1, x2);
+        if (s + D < KS) {
+          issue_x(r0, s + D);
+        } else {
+          issue_x(rn, s + D - KS);
+          if (XADD && xadd) issue_p(s + D - KS);
+        }
+        // the requests stay here, ahead of this k-step's products (nothing but VALU / SALU / LDS work may cross): sunk towards
+        // their use they would have no products to land in
+        __builtin_amdgcn_sched_barrier(0x786);
+      }
       u32x4 a0[4], a1[4], a2[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -354,52 +461,46 @@ __global__ __launch_bounds__(512, 2) void tall_linear_f32x6_k(
       for (int u = 0; u < 4; ++u) acc[t0 + u] = mma32(a1[u], x0, acc[t0 + u]);
 #pragma unroll
       for (int u = 0; u < 4; ++u) acc[t0 + u] = mma32(a0[u], x0, acc[t0 + u]);
-      if ((q + 1) % (G / EMITS) == 0) emit((q + 1) / (G / EMITS) - 1);
+      if ((q + 1) % (G / EMITS) == 0) emit((q + 1) / (G / EMITS) - 1, true);
     }
 #pragma unroll
     for (int T = 0; T < TILES; ++T) pend[T] = acc[T];
     pend_r0 = r0;
     pend_valid = true;
-    if (more) {
-      if (PREFETCH) {
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          xb[s][0] = xn[s][0];
-          xb[s][1] = xn[s][1];
-        }
-        if (xadd) {
-#pragma unroll
-          for (int s = 0; s < KS; ++s) {
-            xb[s][0] += pn[s][0];
-            xb[s][1] += pn[s][1];
-          }
-        }
-      } else {
-        load_x(r0 + 16, xb);
-      }
+    for (int i = 0; i < 2; ++i) {
+      pi[i] = pj[i];
+      ep[i] = ec[i];
+      ec[i] = en[i];
     }
   }
 #pragma unroll
-  for (int tp = 0; tp < EMITS; ++tp) emit(tp);
+  for (int tp = 0; tp < EMITS; ++tp) emit(tp, false);
+}
+
+// one 8-wave workgroup per CU: row blocks x column groups <= 256 workgroups, row blocks a multiple of 8 so that the groups of
+// one row block (ids row_blocks apart) share an XCD and its L2; a wave walks rpw rows (a multiple of 16) in 16-row tiles
+void x6_partition(int64_t m, int groups, int64_t& row_blocks, int64_t& rpw) {
+  row_blocks = (256 / groups) & ~7;
+  rpw = sst_align_up(sst_div_up(m, row_blocks * 8), 16);
+  row_blocks = sst_align_up(sst_div_up(m, rpw * 8), 8);
 }
 
 template <int K, int NW, int EPI, bool XADD = false>
 int launch_x6(const float* x, const float* x2, int x2_from, int64_t ldx, const float* w, int64_t ldw, int trans_w,
               const float* bias, int64_t m, int n, float* y, int64_t ldy, const float* aux_in, float* aux_out, int64_t ldaux,
               hipStream_t st, const ln_epi ln = ln_epi(), const float* xadd_rows = nullptr, const int32_t* xadd_idx = nullptr) {
-  constexpr int lds = 3 * NW * K * 2 + NW * (EPI == kEpiAddLN ? 3 : 1) * 4;
-  static_assert(lds <= 160 * 1024, "three weight images of a column group must fit the CU's LDS");
+  // three weight images of a column group, the bias image (where it fits: x6_bias_in_regs) and one 2 KiB block per wave
+  constexpr int lds = x6_lds_bytes<K, NW, EPI>();
+  static_assert(lds <= 160 * 1024, "three weight images of a column group and the waves' blocks must fit the CU's LDS");
   static unsigned long long configured = 0;
   if (sst_first_use_on_device(&configured)) {
     SST_HIP(hipFuncSetAttribute((const void*)tall_linear_f32x6_k<K, NW, EPI, XADD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     sst_mark_device(&configured);
   }
   const int groups = n / NW;
-  // one 8-wave workgroup per CU: row blocks x column groups <= 256 workgroups, row blocks a multiple of 8 so that the groups of
-  // one row block (ids row_blocks apart) share an XCD and its L2
-  int64_t row_blocks = (256 / groups) & ~7;
-  int64_t rpw = sst_align_up(sst_div_up(m, row_blocks * 8), 16);
-  row_blocks = sst_align_up(sst_div_up(m, rpw * 8), 8);
+  int64_t row_blocks, rpw;
+  x6_partition(m, groups, row_blocks, rpw);
   if (x2 == nullptr) x2_from = groups;
   hipLaunchKernelGGL((tall_linear_f32x6_k<K, NW, EPI, XADD>), dim3((unsigned)(row_blocks * groups)), dim3(512), lds, st, x, x2,
                      x2_from, ldx, w, ldw, trans_w, bias, m, (int)row_blocks, (int)rpw, y, ldy, aux_in, aux_out, ldaux, ln, xadd_rows,
@@ -462,7 +563,7 @@ int sst_tall_linear_epi2_f32x6(const float* d_x, const float* d_x2, int x2_from_
                               d_aux_out, ldaux, st);
   } else if (k == 384 && n == 128) {
     // d(x) of the whole in-projection as ONE product: [dq | dk | dv] (M x 384) times in_proj_weight (384 x 128), the residual
-    // branch's gradient in the epilogue (three images of a 64-column group: 150.5 KB of LDS)
+    // branch's gradient in the epilogue (three images of a 64-column group, 144 KB, + the waves' blocks: all 160 KB of LDS)
     if (d_x2 && (x2_from_col % 64)) return SST_ERR_ARG;
     rc = dispatch_x6<384, 64>(epilogue, d_x, d_x2, x2_from_col / 64, ldx, d_w, ldw, trans_w, d_bias, m, n, d_y, ldy, d_aux_in,
                               d_aux_out, ldaux, st);
@@ -488,6 +589,14 @@ int sst_inproj_pos_f32x6(const float* d_x, int64_t ldx, const float* d_rows, con
                                                      (hipStream_t)stream, ln_epi(), d_rows, d_index);
   if (rc) return rc;
   SST_LAUNCH_CHECK();
+  return SST_OK;
+}
+
+/* How a launch of the kernels above cuts m rows over `groups` column groups (1, 2 or 3): the row blocks per group and the rows
+ * a wave walks.  Host arithmetic only (no launch): the tests take their boundary token counts from it. */
+int sst_tall_linear_f32x6_partition(int64_t m, int groups, int64_t* row_blocks, int64_t* rows_per_wave) {
+  if (m <= 0 || groups < 1 || groups > 3 || !row_blocks || !rows_per_wave) return SST_ERR_ARG;
+  x6_partition(m, groups, *row_blocks, *rows_per_wave);
   return SST_OK;
 }
 
