@@ -1108,6 +1108,17 @@ int64_t sst_spconv_conv_os_f32x6_workspace_bytes_rows(int kvol, int cin, int cou
 int sst_spconv_conv_os_rows_f32x6(const float* d_x, int64_t ldx, const int32_t* d_map, int64_t m, int kvol, const float* d_w,
                                   int cin, int cout, int trans_w, const float* d_bias, float* d_y, int64_t ldy, int tile_cfg,
                                   const int32_t* d_tile_order, void* d_workspace, int64_t workspace_bytes, void* stream);
+/*   sst_spconv_conv_os_plan: what a call of one of the four entries above would launch (host only, nothing runs): rows per
+ *     tile (64 | 128), columns per workgroup (64 | 128), the offset split the call really uses (after the rows entry's own
+ *     halving against workspace_bytes; 1 for the others, which ignore workspace_bytes) and the workgroups launched (the
+ *     padded grid).  Computed by the functions the launches call.  Same error codes as the entry for m, kvol, cin, cout,
+ *     tile_cfg and workspace_bytes; m >= 1. */
+#define SST_SPCONV_OS_ENTRY_F32 0
+#define SST_SPCONV_OS_ENTRY_F32X3 1
+#define SST_SPCONV_OS_ENTRY_F32X6 2
+#define SST_SPCONV_OS_ENTRY_ROWS_F32X6 3
+int sst_spconv_conv_os_plan(int entry, int64_t m, int kvol, int cin, int cout, int tile_cfg, int64_t workspace_bytes,
+                            int32_t* tile_rows, int32_t* cols, int32_t* n_split, int64_t* workgroups);
 /*   sst_spconv_wgrad_os_f32: the same filter gradient as sst_spconv_wgrad_f32 (indiceConvBackward, spconv_ops.h:359-446)
  *     with the gathered rows staged through LDS transposed, 64 x 64 blocks of dW[k], 2048-pair chunks (csrc/spconv_os.hip).
  *     cin % 4 == 0, cout % 4 == 0, row strides % 4 == 0, 16-byte aligned operands; SST_ERR_UNSUPPORTED otherwise. */
@@ -1115,6 +1126,10 @@ int64_t sst_spconv_wgrad_os_workspace_bytes(int kvol, int64_t pair_ld, int64_t t
 int sst_spconv_wgrad_os_f32(const float* d_x, int64_t ldx, const float* d_dy, int64_t lddy, const int32_t* d_pairs,
                             int64_t pair_ld, int64_t total_pairs, int x_side, const int32_t* d_num, int kvol, int cin,
                             int cout, float* d_dw, void* d_workspace, void* stream);
+/*   sst_spconv_wgrad_os_plan: pairs per chunk (512 .. 2048) and the chunk slots (workgroups along x, partials in the
+ *     workspace) of a call of sst_spconv_wgrad_os_f32 / _f32x6 with these arguments (host only). */
+int sst_spconv_wgrad_os_plan(int kvol, int64_t pair_ld, int64_t total_pairs, int cin, int cout, int32_t* chunk_pairs,
+                             int64_t* chunk_slots);
 /*   sst_spconv_wgrad_os_f32x6: the same gradient from the exact three-way bf16 split of both gathered operands (six products on the
  *   bf16 matrix pipe, fp32 accumulation, two accumulator sets; csrc/spconv_os.hip sp_wgrad_os_x6_k): the filter-gradient half of
  *   the 'f32x6' convolution precision.  Same arguments and workspace as sst_spconv_wgrad_os_f32. */

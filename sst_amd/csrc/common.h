@@ -81,6 +81,13 @@ int sst_internal_encoder_tail_bwd_bf16(const sst_encoder_tail_bwd_bf16_args* arg
 int sst_internal_weight_grad_group_f32x6(const sst_wgrad_problem_f32* problems, int n, void* d_workspace,
                                          const sst_colsum_rider* riders, int n_riders, void* stream);
 
+// Launch plans of the split sparse convolutions (csrc/spconv_os_x3.hip, csrc/spconv_os_x6.hip), computed by the functions
+// their launches call, for sst_spconv_conv_os_plan (csrc/spconv_os.hip).  rows: the entry that is told its workspace.
+int sst_internal_spconv_x3_plan(int64_t m, int kvol, int cin, int cout, int32_t* tile_rows, int32_t* cols, int32_t* n_split,
+                                int64_t* workgroups);
+int sst_internal_spconv_x6_plan(int rows, int64_t m, int kvol, int cin, int cout, int64_t workspace_bytes, int32_t* tile_rows,
+                                int32_t* cols, int32_t* n_split, int64_t* workgroups);
+
 // Workspace carving on the host side (256-byte aligned slices of one caller-owned buffer).
 struct sst_carver {
   char* base;

@@ -704,6 +704,23 @@ os_cfg os_pick(int64_t m, int cout, int tile_cfg) {
   return c;
 }
 
+// numbering of a launch of n_units workgroups: XCD runs of kOsXcdChunk from 64 runs on, the grid padded to whole rounds of runs
+struct os_grid {
+  int chunk;
+  int64_t grid;
+};
+os_grid os_number(int64_t n_units) {
+  static int xcd_chunk = -1;  // SST_SPCONV_OS_XCD_CHUNK: units per run (A/B measurements)
+  if (xcd_chunk < 0) {
+    const char* e = getenv("SST_SPCONV_OS_XCD_CHUNK");
+    xcd_chunk = e && atoi(e) > 0 ? atoi(e) : kOsXcdChunk;
+  }
+  os_grid g;
+  g.chunk = n_units >= 64 * (int64_t)xcd_chunk ? xcd_chunk : 1;
+  g.grid = sst_div_up(n_units, 8 * g.chunk) * 8 * g.chunk;
+  return g;
+}
+
 }  // namespace
 
 extern "C" {
@@ -733,13 +750,9 @@ int sst_spconv_conv_os_f32(const float* d_x, int64_t ldx, const int32_t* d_map, 
   const int64_t packed = (int64_t)kvol * c.n_cg * n_cc * 64 * 16 * c.nct;
   hipLaunchKernelGGL(sp_os_pack_w_k, dim3(sst_grid_1d(packed, 256)), dim3(256), 0, st, d_w, kvol, cin, cout, trans_w,
                      c.nct, c.n_cg, n_cc, wp);
-  static int xcd_chunk = -1;  // SST_SPCONV_OS_XCD_CHUNK: units per run (A/B measurements)
-  if (xcd_chunk < 0) {
-    const char* e = getenv("SST_SPCONV_OS_XCD_CHUNK");
-    xcd_chunk = e && atoi(e) > 0 ? atoi(e) : kOsXcdChunk;
-  }
-  const int chunk = n_units >= 64 * (int64_t)xcd_chunk ? xcd_chunk : 1;
-  const dim3 grid((unsigned)(sst_div_up(n_units, 8 * chunk) * 8 * chunk));
+  const os_grid g = os_number(n_units);
+  const int chunk = g.chunk;
+  const dim3 grid((unsigned)g.grid);
   const int vec_store = ((ldy & 3) == 0 && (((uintptr_t)d_y) & 15) == 0 && (!d_bias || (((uintptr_t)d_bias) & 15) == 0)) ? 1 : 0;
 #define SST_OS_LAUNCH(NCT, RB)                                                                                         \
   do {                                                                                                                 \
@@ -772,6 +785,29 @@ int sst_spconv_conv_os_tile_rows(int64_t m, int cout, int tile_cfg) {
   return 64 * os_pick(m, cout, tile_cfg).rb;
 }
 
+int sst_spconv_conv_os_plan(int entry, int64_t m, int kvol, int cin, int cout, int tile_cfg, int64_t workspace_bytes,
+                            int32_t* tile_rows, int32_t* cols, int32_t* n_split, int64_t* workgroups) {
+  if (m < 1 || kvol < 1 || cin < 1 || cout < 1 || !tile_rows || !cols || !n_split || !workgroups) return SST_ERR_ARG;
+  if (entry == SST_SPCONV_OS_ENTRY_F32) {
+    if (tile_cfg != 0 && tile_cfg != 41 && tile_cfg != 42 && tile_cfg != 81 && tile_cfg != 82) return SST_ERR_ARG;
+    if (kvol > kOsMaxK || (cin & 3)) return SST_ERR_UNSUPPORTED;
+    const os_cfg c = os_pick(m, cout, tile_cfg);
+    const int64_t n_units = c.n_tiles * c.n_cg;
+    if (n_units > 0x3fffffff) return SST_ERR_UNSUPPORTED;
+    *tile_rows = 64 * c.rb;
+    *cols = 16 * c.nct;
+    *n_split = 1;
+    *workgroups = os_number(n_units).grid;
+    return SST_OK;
+  }
+  if (tile_cfg != 0) return SST_ERR_ARG;
+  if (entry == SST_SPCONV_OS_ENTRY_F32X3) return sst_internal_spconv_x3_plan(m, kvol, cin, cout, tile_rows, cols, n_split, workgroups);
+  if (entry == SST_SPCONV_OS_ENTRY_F32X6 || entry == SST_SPCONV_OS_ENTRY_ROWS_F32X6)
+    return sst_internal_spconv_x6_plan(entry == SST_SPCONV_OS_ENTRY_ROWS_F32X6, m, kvol, cin, cout, workspace_bytes, tile_rows, cols,
+                                       n_split, workgroups);
+  return SST_ERR_ARG;
+}
+
 int sst_spconv_os_tile_work_i32(const int32_t* d_map, int64_t m, int kvol, int tile_rows, int32_t* d_work, void* stream) {
   if (m < 0 || kvol < 1 || (tile_rows != 64 && tile_rows != 128)) return SST_ERR_ARG;
   if (m == 0) return SST_OK;
@@ -797,6 +833,16 @@ int64_t sst_spconv_wgrad_os_workspace_bytes(int kvol, int64_t pair_ld, int64_t t
   const int n_blocks = (int)(sst_div_up(cin > 0 ? cin : 1, 64) * sst_div_up(cout > 0 ? cout : 1, 64));
   const int csize = os_wgrad_chunk_size(kvol, pair_ld, total_pairs, n_blocks);
   return os_wgrad_chunks(kvol, pair_ld, total_pairs, csize) * cin * cout * (int64_t)sizeof(float) + 256;
+}
+
+int sst_spconv_wgrad_os_plan(int kvol, int64_t pair_ld, int64_t total_pairs, int cin, int cout, int32_t* chunk_pairs,
+                             int64_t* chunk_slots) {
+  if (kvol < 1 || cin < 1 || cout < 1 || pair_ld < 1 || !chunk_pairs || !chunk_slots) return SST_ERR_ARG;
+  const int n_bi = (int)sst_div_up(cin, 64), n_bj = (int)sst_div_up(cout, 64);
+  const int csize = os_wgrad_chunk_size(kvol, pair_ld, total_pairs, n_bi * n_bj);
+  *chunk_pairs = csize;
+  *chunk_slots = os_wgrad_chunks(kvol, pair_ld, total_pairs, csize);
+  return SST_OK;
 }
 
 static int wgrad_os_any(int split, const float* d_x, int64_t ldx, const float* d_dy, int64_t lddy, const int32_t* d_pairs,

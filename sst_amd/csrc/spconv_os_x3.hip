@@ -228,6 +228,25 @@ __global__ __launch_bounds__(256, NCT == 4 ? 4 : 2) void sp_conv_os_x3_k(
   }
 }
 
+// tile shape and launch of a call: 128 columns per workgroup only while that leaves a few workgroups per CU (as
+// sp_conv_os_k's os_pick), XCD runs of kX3XcdChunk from 64 runs on, the grid padded to whole rounds of runs
+struct x3_cfg {
+  int nct, n_cg, n_cc, chunk;
+  int64_t n_tiles, n_units, grid;
+};
+x3_cfg x3_pick(int64_t m, int cin, int cout) {
+  x3_cfg c;
+  c.n_tiles = sst_div_up(m, 64);
+  c.nct = cout <= 64 ? 4 : 8;
+  if (c.nct == 8 && c.n_tiles * sst_div_up(cout, 128) < 2048) c.nct = 4;
+  c.n_cg = (int)sst_div_up(cout, 16 * c.nct);
+  c.n_cc = (int)sst_div_up(cin, kX3Chunk);
+  c.n_units = c.n_tiles * c.n_cg;
+  c.chunk = c.n_units >= 64 * (int64_t)kX3XcdChunk ? kX3XcdChunk : 1;
+  c.grid = sst_div_up(c.n_units, 8 * c.chunk) * 8 * c.chunk;
+  return c;
+}
+
 }  // namespace
 
 extern "C" {
@@ -242,19 +261,17 @@ int sst_spconv_conv_os_f32x3(const float* d_x, int64_t ldx, const int32_t* d_map
   if (kvol > kX3MaxK || (cin & 3) || (ldx & 3) || (((uintptr_t)d_x) & 15) || (((uintptr_t)d_workspace) & 15) ||
       m > 0x3fffffff)
     return SST_ERR_UNSUPPORTED;
-  const int64_t n_tiles = sst_div_up(m, 64);
-  int nct = cout <= 64 ? 4 : 8;
-  if (nct == 8 && n_tiles * sst_div_up(cout, 128) < 2048) nct = 4;   // as sp_conv_os_k's os_pick
-  const int n_cg = (int)sst_div_up(cout, 16 * nct), n_cc = (int)sst_div_up(cin, kX3Chunk);
-  const int64_t n_units = n_tiles * n_cg;
+  const x3_cfg c = x3_pick(m, cin, cout);
+  const int nct = c.nct, n_cg = c.n_cg, n_cc = c.n_cc;
+  const int64_t n_units = c.n_units;
   if (n_units > 0x3fffffff) return SST_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   unsigned* wp = (unsigned*)d_workspace;
   const int64_t lanes = (int64_t)kvol * n_cg * n_cc * 2 * nct * 64;
   hipLaunchKernelGGL(sp_x3_pack_w_k, dim3(sst_grid_1d(lanes, 256)), dim3(256), 0, st, d_w, kvol, cin, cout, trans_w, nct, n_cg,
                      n_cc, wp);
-  const int chunk = n_units >= 64 * (int64_t)kX3XcdChunk ? kX3XcdChunk : 1;
-  const dim3 grid((unsigned)(sst_div_up(n_units, 8 * chunk) * 8 * chunk));
+  const int chunk = c.chunk;
+  const dim3 grid((unsigned)c.grid);
   const int vec_store = ((ldy & 3) == 0 && (((uintptr_t)d_y) & 15) == 0 && (!d_bias || (((uintptr_t)d_bias) & 15) == 0)) ? 1 : 0;
   const int lds = (2 * 64 * 16 * nct + kvol * 64 + 4) * (int)sizeof(unsigned);
   if (nct == 4) {
@@ -281,3 +298,16 @@ int sst_spconv_conv_os_f32x3(const float* d_x, int64_t ldx, const int32_t* d_map
 }
 
 }  // extern "C"
+
+// the launch plan of sst_spconv_conv_os_f32x3; asked by sst_spconv_conv_os_plan (csrc/spconv_os.hip)
+int sst_internal_spconv_x3_plan(int64_t m, int kvol, int cin, int cout, int32_t* tile_rows, int32_t* cols, int32_t* n_split,
+                                int64_t* workgroups) {
+  if (kvol > kX3MaxK || (cin & 3) || m > 0x3fffffff) return SST_ERR_UNSUPPORTED;
+  const x3_cfg c = x3_pick(m, cin, cout);
+  if (c.n_units > 0x3fffffff) return SST_ERR_UNSUPPORTED;
+  *tile_rows = 64;
+  *cols = 16 * c.nct;
+  *n_split = 1;
+  *workgroups = c.grid;
+  return SST_OK;
+}

@@ -304,6 +304,25 @@ x6_cfg x6_pick(int64_t m, int kvol, int cin, int cout) {
   return c;
 }
 
+// what a call on a workspace of workspace_bytes launches: the split halved until its partial tiles fit behind the packed
+// weights, the workgroups numbered in XCD runs of kX6XcdChunk from 64 runs on, the grid padded to whole rounds of runs
+struct x6_launch {
+  x6_cfg c;
+  int64_t pack_bytes, wgs, grid;
+  int chunk;
+};
+x6_launch x6_plan(int64_t m, int kvol, int cin, int cout, int64_t workspace_bytes) {
+  x6_launch p;
+  p.c = x6_pick(m, kvol, cin, cout);
+  p.pack_bytes = sst_align_up(sst_spconv_conv_os_f32x6_workspace_bytes(kvol, cin, cout), 256);
+  const int64_t cpad = (cout + 3) & ~3;
+  while (p.c.n_split > 1 && p.pack_bytes + (int64_t)p.c.n_split * m * cpad * 4 > workspace_bytes) p.c.n_split >>= 1;
+  p.wgs = p.c.n_tiles * p.c.n_cg * p.c.n_split;
+  p.chunk = p.wgs >= 64 * (int64_t)kX6XcdChunk ? kX6XcdChunk : 1;
+  p.grid = sst_div_up(p.wgs, 8 * p.chunk) * 8 * p.chunk;
+  return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -337,10 +356,10 @@ int sst_spconv_conv_os_rows_f32x6(const float* d_x, int64_t ldx, const int32_t* 
   if (kvol > kX6MaxK || (cin & 3) || (ldx & 3) || (((uintptr_t)d_x) & 15) || (((uintptr_t)d_workspace) & 255) ||
       m > 0x3fffffff)
     return SST_ERR_UNSUPPORTED;
-  x6_cfg c = x6_pick(m, kvol, cin, cout);
-  const int64_t pack_bytes = sst_align_up(sst_spconv_conv_os_f32x6_workspace_bytes(kvol, cin, cout), 256);
+  const x6_launch p = x6_plan(m, kvol, cin, cout, workspace_bytes);
+  const x6_cfg& c = p.c;
+  const int64_t pack_bytes = p.pack_bytes;
   const int64_t cpad = (cout + 3) & ~3;
-  while (c.n_split > 1 && pack_bytes + (int64_t)c.n_split * m * cpad * 4 > workspace_bytes) c.n_split >>= 1;
   if (workspace_bytes < c.pack_words * 4) return SST_ERR_ARG;
   const int nct = c.nct, n_cg = c.n_cg, n_cc = c.n_cc;
   const int64_t n_units = c.n_tiles * n_cg;
@@ -351,9 +370,8 @@ int sst_spconv_conv_os_rows_f32x6(const float* d_x, int64_t ldx, const int32_t* 
   const int64_t lanes = (int64_t)kvol * n_cg * n_cc * 2 * nct * 64;
   hipLaunchKernelGGL(sp_x6_pack_w_k, dim3(sst_grid_1d(lanes, 256)), dim3(256), 0, st, d_w, kvol, cin, cout, trans_w, nct, n_cg,
                      n_cc, wp);
-  const int64_t wgs = n_units * c.n_split;
-  const int chunk = wgs >= 64 * (int64_t)kX6XcdChunk ? kX6XcdChunk : 1;
-  const dim3 grid((unsigned)(sst_div_up(wgs, 8 * chunk) * 8 * chunk));
+  const int chunk = p.chunk;
+  const dim3 grid((unsigned)p.grid);
   const int vec_store = ((ldy & 3) == 0 && (((uintptr_t)d_y) & 15) == 0 && (!d_bias || (((uintptr_t)d_bias) & 15) == 0)) ? 1 : 0;
   const int lds = (2 * 64 * 4 * 2 * nct * 3 + kvol * 64 + 4) * (int)sizeof(unsigned);
   if (nct == 4) {
@@ -394,3 +412,19 @@ int sst_spconv_conv_os_f32x6(const float* d_x, int64_t ldx, const int32_t* d_map
 }
 
 }  // extern "C"
+
+// the launch plan of sst_spconv_conv_os_rows_f32x6 on workspace_bytes (rows = 1), or of sst_spconv_conv_os_f32x6 and the
+// packed weights it offers itself; asked by sst_spconv_conv_os_plan (csrc/spconv_os.hip)
+int sst_internal_spconv_x6_plan(int rows, int64_t m, int kvol, int cin, int cout, int64_t workspace_bytes, int32_t* tile_rows,
+                                int32_t* cols, int32_t* n_split, int64_t* workgroups) {
+  if (kvol > kX6MaxK || (cin & 3) || m > 0x3fffffff) return SST_ERR_UNSUPPORTED;
+  if (!rows) workspace_bytes = sst_align_up(sst_spconv_conv_os_f32x6_workspace_bytes(kvol, cin, cout), 256);
+  const x6_launch p = x6_plan(m, kvol, cin, cout, workspace_bytes);
+  if (workspace_bytes < p.c.pack_words * 4) return SST_ERR_ARG;
+  if (p.wgs > 0x3fffffff) return SST_ERR_UNSUPPORTED;
+  *tile_rows = 64;
+  *cols = 16 * p.c.nct;
+  *n_split = p.c.n_split;
+  *workgroups = p.grid;
+  return SST_OK;
+}

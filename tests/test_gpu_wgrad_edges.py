@@ -11,9 +11,16 @@ the last 4-token quad, empty trailing slices) without a copy of any launch plan.
 Recipes (`_values`):
   A  dy, x integers in [-4, 4]                                                  (m up to 2^19; every kernel, bf16 included)
   B  one operand in {-1, 0, 1}, the other k / 1024, |k| <= 2047: 12 significant bits = two non-zero bf16 parts (m <= 4300)
-  C  one operand in {-1, 0, 1}, the other k / 2^17, |k| < 2^17: three non-zero bf16 parts                       (m <= 64)
-B and C are exact in the exact-split mode because the unit operand has one part and every product d_i x_0, i <= 2, is kept.
-The caps of B and C are half of what the condition allows: the leading bf16 part of a value rounds up to at most twice it."""
+  C  one operand in {-1, 0, 1}, the other k / 2^17, |k| < 2^17: 17 bits, which still are TWO non-zero bf16 parts - under
+     round-to-nearest each part gains nine bits (eight and the sign of the remainder); none of the 262 143 values has a
+     third part (tests/test_spconv_exact_host.py)                                                                 (m <= 64)
+  D  one operand k / 2^20, |k| < 2^20: three non-zero bf16 parts in half of the entries; the other in {-1, 0, 1} with at most
+     4 non-zero tokens in any column of it, so that at most 4 terms reach an element of dW at any m               (m <= 130)
+     With the fine operand on the dy side db would be a sum of m fine values (exact only for m < 8): those problems carry no
+     bias gradient.  The recipe that notices a dropped or misplaced x2 w0 / x0 w2 product or third LDS image.
+B, C and D are exact in the exact-split mode because the unit operand has one part and every product d_i x_0, i <= 2, is kept.
+The caps of B and C are half of what the condition allows: the leading bf16 part of a value rounds up to at most twice it; D
+asserts the sum of the absolute products themselves, below 2^23 granules."""
 import functools
 
 import pytest
@@ -27,10 +34,10 @@ P_ROWS = 144                               # rows of the positional table
 M_SWEEP = 4230                             # rows of the pre-generated operands the sweeps cut their prefixes from
 SWEEP_A = range(1, 131)                    # C entries, no gate
 SWEEP_B = range(4090, 4231)                # across the Python gate at 4096 rows
-GRANULE = {'A': 1.0, 'B': 2.0 ** -10, 'C': 2.0 ** -17}
-M_CAP = {'A': 1 << 19, 'B': 4300, 'C': 64}
+GRANULE = {'A': 1.0, 'B': 2.0 ** -10, 'C': 2.0 ** -17, 'D': 2.0 ** -20}
+M_CAP = {'A': 1 << 19, 'B': 4300, 'C': 64, 'D': 130}
 RECIPES_B = [('A', 'dy'), ('B', 'dy'), ('B', 'x')]      # (recipe, the many-valued side): B both ways round
-RECIPES_C = [('A', 'dy'), ('C', 'dy'), ('C', 'x')]
+RECIPES_C = [('A', 'dy'), ('C', 'dy'), ('C', 'x'), ('D', 'dy'), ('D', 'x')]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -43,13 +50,25 @@ def _values(recipe, fine, shape, gen, part=None):
     ri = lambda lo, hi: torch.randint(lo, hi + 1, shape, generator=gen, device=DEV).float()     # noqa: E731
     if recipe == 'A':
         return ri(-4, 4)
-    scale = 1024.0 if recipe == 'B' else 2.0 ** 17
-    top = 2047 if recipe == 'B' else 2 ** 17 - 1
+    if recipe == 'D' and not fine and part is None:
+        return _unit_d(shape, gen)
+    scale = {'B': 1024.0, 'C': 2.0 ** 17, 'D': 2.0 ** 20}[recipe]
+    top = {'B': 2047, 'C': 2 ** 17 - 1, 'D': 2 ** 20 - 1}[recipe]
     if part is None:
         return ri(-top, top) / scale if fine else ri(-1, 1)
     if fine:
         return (ri(-(top // 2), top // 2) if part == 'x' else ri(-(top // 2) - 1, top // 2 + 1)) / scale
     return ri(0, 1) if part == 'x' else ri(-1, 0)
+
+
+def _unit_d(shape, gen):
+    """the unit operand of recipe D: [rows, cols] of {-1, 0, 1} with 4 non-zero tokens (fewer than 4 rows: all of them) in
+    every column, at rows drawn per column"""
+    rows, cols = shape
+    t = torch.zeros(shape, device=DEV)
+    at = torch.rand(shape, generator=gen, device=DEV).argsort(0)[:4]
+    sign = torch.randint(0, 2, at.shape, generator=gen, device=DEV).float() * 2 - 1
+    return t.scatter_(0, at, sign)
 
 
 class _Prob:
@@ -85,6 +104,12 @@ class _Prob:
 def _assert_exact(recipe, m, probs):
     """the condition under which every partial sum is an fp32 number - before anything is launched"""
     assert 1 <= m <= M_CAP[recipe], (recipe, m)
+    if recipe == 'D':               # no bound from m: the absolute products themselves, summed
+        for p in probs:
+            mm = p.m_of(m)
+            assert float((p.dyd[:mm].abs().t() @ p.xd[:mm].abs()).max()) / GRANULE['D'] < 2 ** 23, (m, p.out, p.inn)
+            assert not p.bias or float(p.dyd[:mm].abs().sum(0).max()) / GRANULE['D'] < 2 ** 23, (m, p.out)
+        return
     for p in probs:
         assert m * p.dy_max * p.x_max / GRANULE[recipe] < 2 ** 24, (recipe, m, p.dy_max, p.x_max)
         assert m * p.dy_max / GRANULE[recipe] < 2 ** 24
@@ -95,7 +120,7 @@ class _Layer:
     (ds1, o) (dqkv[:, :256], xp) (dqkv[:, 256:], x), the last two as column views of one [M, 384] buffer; `pos`: the fourth
     problem reads xq + table[index] instead of xp"""
 
-    def __init__(self, recipe, fine, rows, seed=0, gaussian=False):
+    def __init__(self, recipe, fine, rows, seed=0, gaussian=False, bias=True):
         gen = torch.Generator(device=DEV).manual_seed(1000 * seed + rows + ord(recipe) + (7 if fine == 'x' else 0))
         if gaussian:
             mk = lambda side, cols, part=None: torch.randn((rows, cols), generator=gen, device=DEV)      # noqa: E731
@@ -105,25 +130,33 @@ class _Layer:
             self.table = _values(recipe, fine == 'x', (P_ROWS, 128), gen, 'table')
         self.dqkv, self.ds2, self.ds1, self.dpre = mk('dy', 384), mk('dy', 128), mk('dy', 128), mk('dy', 256)
         self.h, self.y1, self.o, self.xp, self.x = mk('x', 256), mk('x', 128), mk('x', 128), mk('x', 128), mk('x', 128)
-        self.xq = mk('x', 128, 'x')
+        unit_d_x = recipe == 'D' and fine != 'x' and not gaussian
+        self.xq = None if unit_d_x else mk('x', 128, 'x')
         index = torch.randint(0, P_ROWS, (rows,), generator=gen, device=DEV, dtype=torch.int32)
         # the first and the last row of the table and repeats, from the first tokens on and at the very end
         head = torch.tensor([P_ROWS - 1, 0, 0, P_ROWS - 1, 7, 7, 7, P_ROWS - 1], dtype=torch.int32, device=DEV)[:rows]
         index[:head.numel()] = head
         index[-1] = P_ROWS - 1 if rows > 1 else index[-1]
         self.index = index
-        self.w2, self.w1 = _Prob(self.ds2, self.h), _Prob(self.dpre, self.y1)
-        self.wo, self.wv = _Prob(self.ds1, self.o), _Prob(self.dqkv[:, 256:], self.x)
-        self.wqk = _Prob(self.dqkv[:, :256], self.xp)
-        self.wqk_pos = _Prob(self.dqkv[:, :256], self.xq, (self.table, self.index))
+        if unit_d_x:                # x + table[index] is a unit operand of recipe D; x and the table hold small integers
+            self.xq = _unit_d((rows, 128), gen) - self.table[index.long()]
+        self.w2, self.w1 = _Prob(self.ds2, self.h, bias=bias), _Prob(self.dpre, self.y1, bias=bias)
+        self.wo, self.wv = _Prob(self.ds1, self.o, bias=bias), _Prob(self.dqkv[:, 256:], self.x, bias=bias)
+        self.wqk = _Prob(self.dqkv[:, :256], self.xp, bias=bias)
+        self.wqk_pos = _Prob(self.dqkv[:, :256], self.xq, (self.table, self.index), bias=bias)
         self.group1, self.group2 = [self.w2, self.w1], [self.wo, self.wqk, self.wv]
         self.group2_pos = [self.wo, self.wqk_pos, self.wv]
         self.five, self.five_pos = self.group1 + self.group2, self.group1 + self.group2_pos
 
 
+def _with_bias(recipe, fine):
+    """recipe D with the fine operand on the dy side: db would be a sum of m fine values - those problems carry none"""
+    return not (recipe == 'D' and fine == 'dy')
+
+
 @functools.lru_cache(maxsize=None)
 def _layer(recipe, fine):
-    return _Layer(recipe, fine, min(M_SWEEP, M_CAP[recipe]))
+    return _Layer(recipe, fine, min(M_SWEEP, M_CAP[recipe]), bias=_with_bias(recipe, fine))
 
 
 @functools.lru_cache(maxsize=None)
@@ -131,7 +164,8 @@ def _extra(recipe, fine, out, inn):
     """a single problem of its own operands, cut like the layer's"""
     rows = min(M_SWEEP, M_CAP[recipe])
     gen = torch.Generator(device=DEV).manual_seed(out * 4099 + inn + ord(recipe))
-    return _Prob(_values(recipe, fine == 'dy', (rows, out), gen), _values(recipe, fine == 'x', (rows, inn), gen))
+    return _Prob(_values(recipe, fine == 'dy', (rows, out), gen), _values(recipe, fine == 'x', (rows, inn), gen),
+                 bias=_with_bias(recipe, fine))
 
 
 class _Tally:
@@ -228,7 +262,8 @@ def _c_single(p, m, guard=0):
 def test_sweep_a_c_entries_every_m_from_1_to_130(recipe, fine):
     """the public C entries accept any m >= 1 and no Python caller goes below 4096: the five-problem layer group through
     sst_weight_grad_group_f32x6 (up to 7 of its 8 slices empty) and sst_weight_grad_group_f32, sst_weight_grad_f32 on 128 x 128
-    and on 1024 x 256 (32 tiles), every m of 1 .. 130 (recipe C: 1 .. 64, where it is exact)"""
+    and on 1024 x 256 (32 tiles), every m of 1 .. 130 (recipe C: 1 .. 64, where it is exact; recipe D, the one with a third
+    bf16 part: 1 .. 130, 4 terms per element at any m)"""
     L = _layer(recipe, fine)
     big = _extra(recipe, fine, 1024, 256)
     tally = _Tally()
