@@ -306,7 +306,10 @@ int sst_window_plan_i32(const int32_t* d_vcoors, const int32_t* d_grid, int64_t 
  * 128/8, 192/12 in every SST config); n_heads must be a multiple of 4.
  * Q,K,V,O: [M, n_heads*16] fp32 with row strides ldq/ldk/ldv/ldo (elements, multiples of 4; base
  * pointers 16-byte aligned).  d_lse [M, n_heads] fp32: log-sum-exp of each softmax row (for backward).
- *   max_tokens: upper bound on tokens per window the caller guarantees (0 = unknown).
+ *   max_tokens: upper bound on tokens per window the caller guarantees (0 = unknown).  It must be an upper bound of EVERY
+ *     window of the call (inclusive: a window of exactly max_tokens tokens is fine): it picks the register class of the
+ *     launch, and a window longer than announced (but <= 144 tokens) is skipped by the register-resident kernels and picked
+ *     up by no other - its output rows keep whatever the buffers held.  The bf16 and cosine calls below take the same bound.
  *   d_tok == NULL: the tokens of window w are the rows winoff[w] .. winoff[w+1] - 1 themselves (feature rows kept in
  *     window order, as sst_window_plan_i32 numbers them for the unshifted partition): no token list is read; taken by the
  *     register-resident kernels only (impl 0 / 3, 0 < max_tokens <= 144, aligned operands), else SST_ERR_UNSUPPORTED.
