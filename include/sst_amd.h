@@ -1354,6 +1354,90 @@ int sst_seg_loss_bwd_f32(const float* d_logits, const float* d_vote_preds, const
                          const float* d_class_weight, const float* d_g, const int64_t* d_counts, float* d_dlogits,
                          float* d_dvote_preds, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training and decoding side of CenterHead (csrc/center_head.hip).  fp32 data, everything on `stream`, no float atomics, no
+ * host read-back, bit-reproducible.
+ *
+ * Targets - replaces CenterHead.get_targets / get_targets_single (mmdet3d/models/dense_heads/centerpoint_head.py:385-560, a
+ * Python loop over every box of every sample), gaussian_radius / draw_heatmap_gaussian / gaussian_2d
+ * (mmdet3d/core/utils/gaussian.py:5-85) and LiDARInstance3DBoxes.gravity_center.  One memset over d_out and one launch for all
+ * samples and tasks.
+ *   d_boxes [n_boxes, box_cols] fp32, box_cols 7 or 9: (x, y, z_bottom, w, l, h, rz [, vx, vy]) of all samples, d_labels int64
+ *   [n_boxes], sample s = boxes d_box_offsets[s] .. d_box_offsets[s + 1] (device int32 [batch + 1]).  task_table: HOST int32
+ *   [n_tasks][2] = (first class, class count), n_tasks <= SST_CENTER_MAX_TASKS.  The feature map is W = grid_x /
+ *   out_size_factor by H = grid_y / out_size_factor; point_cloud_range and voxel_size are HOST float arrays of which [0], [1]
+ *   are read.  Slot k of a task is the box's rank in the reference's class-grouped list (all boxes of the task's first class in
+ *   input order, then the second ...; labels outside the task are not in it); ranks >= max_objs do not exist.  A box whose w or
+ *   l is <= 0 in cells keeps its rank and is skipped, so is a box whose centre cell (truncation toward zero of
+ *   (x - pc_range) / voxel_size / out_size_factor, so a coordinate in (-1, 0) is cell 0) lies outside the map.
+ *   radius = max(min_radius, (int)gaussian_radius((l, w) in cells, gaussian_overlap)) in the reference's fp32 operation order,
+ *   roots correctly rounded; heatmap[class] = max(heatmap[class], exp(-(dx^2 + dy^2) / (2 sigma^2))), sigma = (2 radius + 1) /
+ *   6, over the patch clipped to the map, evaluated in fp64 and rounded to fp32.
+ *   d_out: one allocation of sst_center_targets_layout(...) bytes; that call also fills HOST offsets[4 * n_tasks] with the byte
+ *   offsets (multiples of 256) of each task's heatmap [batch, classes, H, W] fp32, anno_box [batch, max_objs, 10] fp32
+ *   (x - cell, y - cell, z_bottom + h * 0.5, log(w, l, h) when norm_bbox else w, l, h, sin rz, cos rz, vx, vy; 0 velocities for
+ *   7 columns), ind [batch, max_objs] int64 (y * W + x) and mask [batch, max_objs] uint8.  Empty slots are zero.
+ *   sst_center_targets_box_tile(): boxes per workgroup.
+ *
+ * Losses of one task - replaces CenterHead.loss :563-610 (clip_sigmoid, GaussianFocalLoss, the concatenation / permute /
+ * _gather_feat :360-383 of the regression maps, L1Loss) and autograd's backward of it.
+ *   d_logits, d_heatmap [batch, classes, H, W] (hw = H * W): p = clamp(sigmoid(z), 1e-4, 1 - 1e-4),
+ *     loss_heatmap = weight_cls * sum(-log(p + 1e-12) (1 - p)^2 [t == 1] - log(1 - p + 1e-12) p^2 (1 - t)^4) / max(#(t == 1), 1)
+ *   (mmdet 2.x gaussian_focal_loss, alpha 2, gamma 4; mmdet is not in the reference tree).  The logits are not modified.
+ *   d_heads: HOST array of 5 device pointers (reg, height, dim, rot, vel), NCHW with head_channels[5] (HOST; 0 = absent, at most
+ *   10 in all); channel c of their concatenation is compared with column c of d_anno [batch, max_objs, 10] at cell d_ind[b, k]:
+ *     loss_bbox = weight_bbox * sum(|pred - target| mask code_weights[c]) / (sum(mask) + 1e-4),   code_weights: HOST float[10]
+ *   (the denominator is formed in fp32, as the reference's avg_factor = mask.float().sum() + 1e-4 is)
+ *   A masked slot whose ind is outside [0, hw) adds nothing (the reference's gather raises).  Targets are assumed finite.
+ *   d_out float [2]: loss_heatmap, loss_bbox.  d_counts int64 [2]: #(t == 1), sum(mask).
+ *   Forward = a launch writing one record per sst_center_loss_tile_cells() cells into d_workspace
+ *   (sst_center_loss_workspace_bytes(batch * classes * hw)) and a one-workgroup launch that adds the records in index order and
+ *   computes the box loss; sums are carried in fp64 from the lane on.  Backward: d_g_heatmap, d_g_bbox (device scalars, the
+ *   upstream gradients of the two losses; NULL = zero) and the forward's d_counts -> d_dlogits (every element written; zero where the clamp is active) and d_dheads, one allocation of
+ *   batch * sum(head_channels) * hw floats holding the gradients of the present heads one after the other: a memset, the
+ *   element-wise heatmap launch and one launch with a workgroup per sample, in which the lowest slot of each cell adds the
+ *   contributions sign(pred - target) weight / denominator of all slots naming that cell in slot order (sign(0) = 0).
+ *   max_objs <= sst_center_loss_max_objs() in the backward.
+ *
+ * Decoding - replaces CenterPointBBoxCoder.decode (mmdet3d/core/bbox/coders/centerpoint_bbox_coders.py:115-227) after its
+ * _topk.  d_inds int64 / d_scores fp32 [batch, k]: cell indices in [0, hw) and scores.  d_maps: HOST array of 6 device pointers
+ * (reg 2 channels, height 1, dim 3, rot_sine 1, rot_cosine 1, vel 2; reg and vel may be NULL), each with channels hw floats
+ * apart and samples batch_strides[m] floats apart (HOST int64 [6]).  Per index: x = ((cell % W) + reg0 [or 0.5]) *
+ * out_size_factor * voxel_size[0] + pc_range[0], y likewise with (int)((float)cell / W), z = height, dim (exp when norm_bbox),
+ * atan2(sine, cosine), vel -> d_boxes [batch, k, 9 or 7 without vel]; d_keep uint8 [batch, k] = (score > score_threshold when
+ * has_score_threshold) and (post_center_range[0..2] <= (x, y, z) <= post_center_range[3..5] when given; HOST float[6]).  An index
+ * outside the map gives a zero box that is not kept.
+ *
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer or a size < 1; SST_ERR_UNSUPPORTED for box_cols other
+ * than 7 / 9, more than 10 head channels, a map of 2^31 cells or more, or max_objs above the backward's limit.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_CENTER_MAX_TASKS 8
+int sst_center_targets_box_tile(void);
+int64_t sst_center_targets_layout(int batch, int n_tasks, const int32_t* task_table, int grid_x, int grid_y,
+                                  int out_size_factor, int max_objs, int64_t* offsets);
+int sst_center_targets_f32(const float* d_boxes, int box_cols, const int64_t* d_labels, const int32_t* d_box_offsets,
+                           int64_t n_boxes, int batch, const int32_t* task_table, int n_tasks, int grid_x, int grid_y,
+                           const float* point_cloud_range, const float* voxel_size, int out_size_factor,
+                           double gaussian_overlap, int min_radius, int max_objs, int norm_bbox, void* d_out, void* stream);
+int sst_center_loss_tile_cells(void);
+int sst_center_loss_max_objs(void);
+int64_t sst_center_loss_workspace_bytes(int64_t n_cells);
+int sst_center_loss_fwd_f32(const float* d_logits, const float* d_heatmap, int batch, int classes, int64_t hw,
+                            const float* const* d_heads, const int32_t* head_channels, const float* d_anno,
+                            const int64_t* d_ind, const uint8_t* d_mask, int max_objs, const float* code_weights,
+                            float weight_cls, float weight_bbox, float* d_out, int64_t* d_counts, void* d_workspace,
+                            void* stream);
+int sst_center_loss_bwd_f32(const float* d_logits, const float* d_heatmap, int batch, int classes, int64_t hw,
+                            const float* const* d_heads, const int32_t* head_channels, const float* d_anno,
+                            const int64_t* d_ind, const uint8_t* d_mask, int max_objs, const float* code_weights,
+                            float weight_cls, float weight_bbox, const float* d_g_heatmap, const float* d_g_bbox,
+                            const int64_t* d_counts, float* d_dlogits, float* d_dheads, void* stream);
+int sst_center_decode_f32(const int64_t* d_inds, const float* d_scores, int batch, int k, int grid_w, int64_t hw,
+                          const float* const* d_maps, const int64_t* batch_strides, int out_size_factor,
+                          const float* voxel_size, const float* pc_range, int norm_bbox, int has_score_threshold,
+                          float score_threshold, const float* post_center_range, float* d_boxes, uint8_t* d_keep,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,9 @@ from . import detectors  # noqa: F401
 from .detectors import (DETECTORS, HEADS, NECKS, FSD, FSDV2, DynamicCenterPoint, DynamicVoxelNet, SingleStageFSD, SingleStageFSDV2, VoteSegHead,  # noqa: F401
                         VoteSegmentor, Voxel2PointScatterNeck, build_detector, build_head, build_model, build_neck,
                         install_fused_extract_feat)
+from . import center_head  # noqa: F401
+from .center_head import (BBOX_CODERS, CenterHead, CenterPointBBoxCoder, build_bbox_coder, center_decode, center_loss,  # noqa: F401
+                          center_targets)
 
 __version__ = '0.1.0'
 
@@ -66,4 +69,6 @@ __all__ = [
     'furthest_point_sample', 'furthest_point_sample_with_dist', 'fps_segmented', 'ssg_assign', 'ssg', 'ssg_single_sample',
     'SSGAssigner', 'HybridAssigner', 'sir_stage', 'sir_stage_ok', 'sir_stage_tile_rows', 'enable_fused_sir',
     'seg_loss', 'seg_point_targets', 'seg_vote_loss',
+    'center_head', 'center_targets', 'center_loss', 'center_decode', 'CenterHead', 'CenterPointBBoxCoder', 'BBOX_CODERS',
+    'build_bbox_coder',
 ]

@@ -345,6 +345,19 @@ _SIGNATURES = {
                                                    c_ptr, c_ptr, c_ptr]),
     'sst_seg_loss_bwd_f32': (c_i32, [c_ptr] * 5 + [c_i64, c_i32, c_i32, c_f32, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                                    c_ptr]),
+    'sst_center_targets_box_tile': (c_i32, []),
+    'sst_center_targets_layout': (c_i64, [c_i32, c_i32, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr]),
+    'sst_center_targets_f32': (c_i32, [c_ptr, c_i32, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_i32,
+                                       ctypes.c_double, c_i32, c_i32, c_i32, c_ptr, c_ptr]),
+    'sst_center_loss_tile_cells': (c_i32, []),
+    'sst_center_loss_max_objs': (c_i32, []),
+    'sst_center_loss_workspace_bytes': (c_i64, [c_i64]),
+    'sst_center_loss_fwd_f32': (c_i32, [c_ptr, c_ptr, c_i32, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_f32,
+                                        c_f32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_center_loss_bwd_f32': (c_i32, [c_ptr, c_ptr, c_i32, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_f32,
+                                        c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_center_decode_f32': (c_i32, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_i32, c_i32,
+                                      c_f32, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
