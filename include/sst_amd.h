@@ -565,6 +565,12 @@ int sst_weight_grad_group_f32(const sst_wgrad_problem_f32* problems, int n, void
  * uses sst_weight_grad_group_f32. */
 int64_t sst_weight_grad_group_f32x6_workspace_bytes(const sst_wgrad_problem_f32* problems, int n);
 int sst_weight_grad_group_f32x6(const sst_wgrad_problem_f32* problems, int n, void* d_workspace, void* stream);
+/* Host only: the launch plan of that group, from the function the launch itself uses - 128 x 128 tiles over all problems, token
+ * slices per tile, tokens per slice (a multiple of 32), and how many of the slices (the first ones) run their steady state in
+ * the kernel's lean loop: full steps only, every requested row inside [0, m).  Outputs may be NULL.  SST_ERR_UNSUPPORTED as
+ * the workspace query. */
+int sst_weight_grad_group_f32x6_plan(const sst_wgrad_problem_f32* problems, int n, int* tiles, int* slices,
+                                     int64_t* tokens_per_slice, int* lean_slices);
 
 /* ------------------------------------------------------------------------------------------------
  * (a11/a12, §8 f1) BatchNorm1d (+ ReLU) of the point-wise "Linear -> norm -> ReLU" layers of DynamicVFE / SIR

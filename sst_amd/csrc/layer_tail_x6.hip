@@ -376,6 +376,12 @@ __device__ __forceinline__ void mma_half(const unsigned char* slot, int lane_off
   }
 }
 
+// a + b component by component: beside MFMAs a vector sum would become two v_pk_add_f32, which cost more vector-issue cycles
+// there than the four v_add_f32 (Makefile: this file is built without the SLP vectoriser for the same reason)
+__device__ __forceinline__ f32x4 add4(const f32x4& a, const f32x4& b) {
+  return (f32x4){a[0] + b[0], a[1] + b[1], a[2] + b[2], a[3] + b[3]};
+}
+
 // first product of a feed-forward chunk: 32 output columns (two tiles) over K = 128 from the kept parts of the input tile.
 // Per tile three accumulators - the leading product, the two 2^-8 corrections, the three 2^-16 corrections - so that a
 // dependent MFMA is at least four instructions behind its predecessor with the fragments of ONE k-step in registers, and the
@@ -406,8 +412,8 @@ __device__ __forceinline__ void mma_first(const unsigned char* slot, int lane_of
 #pragma unroll
     for (int T = 0; T < 2; ++T) cb[T] = mma32(a1[T], y[s].p0, cb[T]);
   }
-  out0 = am[0] + (cb[0] + ca[0]);
-  out1 = am[1] + (cb[1] + ca[1]);
+  out0 = add4(am[0], add4(cb[0], ca[0]));
+  out1 = add4(am[1], add4(cb[1], ca[1]));
 }
 
 // second product of a feed-forward chunk: one k-step (the chunk's 32 hidden columns), 8 output tiles
@@ -565,8 +571,8 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
     f32x4 p0, p1;
     mma_first(lds, lane_off1, yi, p0, p1);
     const int nl = kHC * j + 8 * g;
-    p0 += *(const f32x4*)(par + 6 * kC + nl);
-    p1 += *(const f32x4*)(par + 6 * kC + nl + 4);
+    p0 = add4(p0, *(const f32x4*)(par + 6 * kC + nl));
+    p1 = add4(p1, *(const f32x4*)(par + 6 * kC + nl + 4));
     f32x4 h0, h1;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {

@@ -5,7 +5,12 @@
 // Replaces, in that mode, wgrad_wide_k of csrc/wgrad.hip (exact fp32 matrix pipe: 2.65 + 0.3 ms of the 12.6 ms step, bound
 // by that pipe at 78 % of its sustained rate) for the five parameter gradients of an SRA encoder layer
 // (autograd of sst_basic_block_v2.py:41-126): the contraction runs over the TOKENS, 6 x 16 instead of 8 x 32 matrix-pipe
-// cycles per 16 x 16 x 32 block, so the kernel is bound by reading dY and X once (HBM).
+// cycles per 16 x 16 x 32 block.  The kernel is NOT bound by reading dY and X (it moves the algorithmic bytes at a fraction of
+// the HBM rate) nor by the matrix pipe: it is bound by VECTOR ISSUE - an MFMA holds the SIMD's issue port for 8 cycles, a VALU
+// instruction for 4, both waves of a SIMD share the port, and the staging code (split, masks, addresses) was 238 VALU
+// instructions beside the 48 MFMAs of a step.  Hence the lean steady-state loop below: the row clamps, the
+// `t < t_end` masks and the 64-bit address arithmetic exist only in the general loop that ends every slice, and what depends on
+// the role of a wave (dY or X staging, bias sum, positional add) is decided by scalar branches, not per element.
 //
 // The contraction index is the row index of both operands in memory (token-major rows), while an MFMA operand wants 8
 // consecutive k (= tokens) of ONE column per lane: the transposition happens on the way into LDS.  Per 32-token step a
@@ -23,6 +28,7 @@
 // (fp32) go to the workspace, ONE reduction launch sums them in slice order (deterministic).
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 
 namespace {
@@ -50,9 +56,20 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& p0, unsigned&
   p2 = pack2(ra - lo_f(p1), rb - hi_f(p1));
 }
 
+// a 64-bit value that is the same in all lanes, handed to the scalar side (addresses and loop bounds of the lean loop)
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uint64_t)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// global-memory bytes behind a uniform base: "scalar base + 32-bit lane offset" is an addressing mode of the global loads
+typedef const __attribute__((address_space(1))) char* gbytes;
+
 constexpr int kMaxProblems = 8;
 constexpr int kTile = 128;                    // dW tile: 128 (out) x 128 (in)
 constexpr int kStep = 32;                     // tokens per step
+constexpr int kPf = 2;                        // register sets of the row ring: rows are requested kPf steps ahead (even)
 constexpr int kTileLds = 1040;                // bytes of one 16-column tile image (1 KB + 16-byte skew)
 constexpr int kImage = 8 * kTileLds;          // 128 columns of one part of one operand
 constexpr int kStage = 2 * 3 * kImage;        // both operands, three parts
@@ -73,6 +90,7 @@ struct x6_problem {
 struct x6_group {
   x6_problem p[kMaxProblems];
   int n, tiles, slices;
+  int lean_slices;  // the first lean_slices slices run their steady state in the lean loop (make_plan)
   int64_t tokens_per_slice;
 };
 
@@ -81,7 +99,8 @@ __global__ __launch_bounds__(512, 2) void wgrad_x6_k(const x6_group G, float* __
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
-  const int tile = blockIdx.x / G.slices, slice = blockIdx.x - tile * G.slices;
+  // (the quotient comes out of vector instructions: handed back to the scalar side, where everything derived from it stays)
+  const int tile = __builtin_amdgcn_readfirstlane(blockIdx.x / G.slices), slice = blockIdx.x - tile * G.slices;
   int pi = 0;
 #pragma unroll
   for (int q = 1; q < kMaxProblems; ++q)
@@ -95,7 +114,9 @@ __global__ __launch_bounds__(512, 2) void wgrad_x6_k(const x6_group G, float* __
   t_end = t_end < P.m ? t_end : P.m;
 
   // staging role: threads 0..255 the dY block (columns n0 ..), 256..511 the X block (columns k0 ..): token quad tq, columns 4 cg ..
-  const int op = tid >> 8, tq = (tid >> 5) & 7, cg = tid & 31;
+  // The role is the same for all lanes of a wave (waves 0..3: dY, 4..7: X): taken from lane 0 so that everything that depends
+  // on it - the operand, the bias sum, the positional add - is a scalar value or a scalar branch.
+  const int op = __builtin_amdgcn_readfirstlane(tid >> 8), tq = (tid >> 5) & 7, cg = tid & 31;
   const float* src = op == 0 ? P.dy + n0 + 4 * cg : P.x + k0 + 4 * cg;
   const int64_t ld = op == 0 ? P.ld_dy : P.ld_x;
   // LDS address of this thread's 32 bytes (columns 4 cg .. 4 cg + 3 of tile cg / 4) inside a part image
@@ -105,12 +126,13 @@ __global__ __launch_bounds__(512, 2) void wgrad_x6_k(const x6_group G, float* __
   // (measured: the kernel is NOT bound there - ablations: skeleton of LDS fragment reads + barriers alone 63 of 107 us per group,
   // each wave re-reads 18 fragments (18 KB) per step from LDS for its 48 products - a ring of 4 sets changed nothing).  Loads are UNCONDITIONAL (row clamped, zeroed at the split): no branch
   // around them, so the compiler's vmcnt counts stay exact.
-  constexpr int kPf = 2;
   f32x4 rows[kPf][4];
   const int64_t t_last = t_end > 0 ? t_end - 1 : 0;
   // positional rows of the X operand (x_add_rows): requested with the rows they are added to; their token indices are loaded
   // one request ahead so that a table address never waits for its index
   const bool xadd = op == 1 && P.x_add_rows != nullptr;
+  // the bias gradient is taken from the dY staging waves of the k = 0 tiles of a problem that has one
+  const bool bias = op == 0 && P.db_off >= 0 && tk == 0;
   const float* addsrc = xadd ? P.x_add_rows + k0 + 4 * cg : nullptr;
   f32x4 prow[kPf][4];
   int32_t pidx[4] = {0, 0, 0, 0};
@@ -135,19 +157,66 @@ __global__ __launch_bounds__(512, 2) void wgrad_x6_k(const x6_group G, float* __
       load_idx(t0 + kStep);      // the indices of the NEXT request (requests are one step apart)
     }
   };
+  // the same requests of the lean loop: every row and every index of them is inside [0, m) (make_plan), so there is no clamp,
+  // and the address is a scalar base that moves by 32 rows per step plus a 32-bit lane offset that never changes (row stride
+  // below 2^24 elements, make_plan: 31 rows of it and the columns stay below 2^31 bytes)
+  const int64_t lean_ld4 = uniform64(ld * 4);
+  const gbytes lean_src = (gbytes)uniform64((int64_t)(op == 0 ? P.dy + n0 : P.x + k0)) + uniform64(t_begin) * lean_ld4;
+  const gbytes lean_idx = (gbytes)uniform64((int64_t)(P.x_add_index + t_begin));
+  unsigned lean_off[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lean_off[r] = ((unsigned)(4 * tq + r) * (unsigned)ld + 4u * cg) * 4u;
+  unsigned lean_ioff = 16u * tq;
+  auto load_rows_lean = [&](int64_t s, f32x4 (&dst)[4], f32x4 (&pdst)[4]) {        // the rows of step s of this slice
+    const gbytes base = lean_src + s * kStep * lean_ld4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      // (the empty statement keeps the widening of the offset beside the load: hoisted out of the loop as a 64-bit value it
+      // would cost a 64-bit vector add per load instead of being the load's own offset operand)
+      asm volatile("" : "+v"(lean_off[r]));
+      dst[r] = *(const __attribute__((address_space(1))) f32x4*)(base + lean_off[r]);
+    }
+    if (xadd) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pdst[r] = *(const f32x4*)((const char*)addsrc + (int64_t)pidx[r] * (int64_t)(4 * P.in));
+      const gbytes ib = lean_idx + (s + 1) * kStep * 4;
+      asm volatile("" : "+v"(lean_ioff));
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pidx[r] = *(const __attribute__((address_space(1))) int32_t*)(ib + lean_ioff + 4 * r);
+    }
+  };
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-  // the split of one column (4 tokens) of the staged block: called between the MFMA groups of the running step, so that its ~30
+  // what the role of the wave adds to a staged block before it is split, for the whole block at once and behind scalar
+  // branches: the positional rows (X waves of a problem that has them), the zeroing of the tokens at and beyond t_end (general
+  // loop only: the lean loop stages full steps), the bias sum (dY waves of a tile that owns one).
+  auto finish_rows = [&](auto lean, int64_t t0, f32x4 (&rws)[4], const f32x4 (&prw)[4]) {
+    if (xadd) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rws[r][e] = rws[r][e] + prw[r][e];
+    }
+    if constexpr (!decltype(lean)::value) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool in = t0 + 4 * tq + r < t_end;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rws[r][e] = in ? rws[r][e] : 0.f;
+      }
+    }
+    if (bias) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bsum[e] += (rws[0][e] + rws[1][e]) + (rws[2][e] + rws[3][e]);
+    }
+  };
+  // the split of one column (4 tokens) of the staged block: called between the MFMA groups of the running step, so that its ~22
   // VALU instructions issue in the shadow of the matrix pipe instead of after it (all 8 waves of the workgroup move in lock
   // step from barrier to barrier: work that is not interleaved is serial)
   u32x4 img[3][2];
-  auto split_col = [&](int e, int64_t t0, const f32x4 (&rws)[4], const f32x4 (&prw)[4]) {
-    float v[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = (t0 + 4 * tq + r < t_end) ? (xadd ? rws[r][e] + prw[r][e] : rws[r][e]) : 0.f;
-    if (op == 0) bsum[e] += (v[0] + v[1]) + (v[2] + v[3]);
+  auto split_col = [&](int e, const f32x4 (&rws)[4]) {
     unsigned a0, a1, a2, b0, b1, b2;
-    split2(v[0], v[1], a0, a1, a2);
-    split2(v[2], v[3], b0, b1, b2);
+    split2(rws[0][e], rws[1][e], a0, a1, a2);
+    split2(rws[2][e], rws[3][e], b0, b1, b2);
     img[0][e >> 1][2 * (e & 1)] = a0;
     img[0][e >> 1][2 * (e & 1) + 1] = b0;
     img[1][e >> 1][2 * (e & 1)] = a1;
@@ -185,50 +254,69 @@ __global__ __launch_bounds__(512, 2) void wgrad_x6_k(const x6_group G, float* __
   if (xadd) load_idx(t_begin);
 #pragma unroll
   for (int u = 0; u < kPf; ++u) load_rows(t_begin + (int64_t)u * kStep, rows[u], prow[u]);
+  finish_rows(std::false_type{}, t_begin, rows[0], prow[0]);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) split_col(e, t_begin, rows[0], prow[0]);
+  for (int e = 0; e < 4; ++e) split_col(e, rows[0]);
   store_img(0);
   load_rows(t_begin + (int64_t)kPf * kStep, rows[0], prow[0]);
   __syncthreads();
-  // step s (tokens t_begin + 32 s ..): products on buffer s & 1, and between its four MFMA groups the four columns of step
-  // s + 1 (ring set (s + 1) % kPf) are split; then stored into buffer (s + 1) & 1 and the set refilled with step s + 1 + kPf
+  // step s (tokens t_begin + 32 s ..), ring position u = s % kPf: products on buffer s & 1, and between its four MFMA groups
+  // the four columns of step s + 1 (ring set (s + 1) % kPf) are split; then stored into buffer (s + 1) & 1 and the set refilled
+  // with step s + 1 + kPf.  One body for both loops, one barrier per step, reached by all eight waves.
+  auto step = [&](auto lean, int u, int64_t s) {
+    const int64_t t1 = t_begin + (s + 1) * kStep;
+    f32x4(&rws)[4] = rows[(u + 1) % kPf];
+    f32x4(&prw)[4] = prow[(u + 1) % kPf];
+    finish_rows(lean, t1, rws, prw);
+    const unsigned char* dyi = lds + (u & 1) * kStage;       // dY parts (kPf even: s & 1 == u & 1)
+    const unsigned char* xi = dyi + 3 * kImage;               // X parts
+    u32x4 b0[2], b1[2], b2[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      b0[b] = frag(dyi, 2 * wn + b);
+      b1[b] = frag(dyi + kImage, 2 * wn + b);
+      b2[b] = frag(dyi + 2 * kImage, 2 * wn + b);
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const u32x4 a0 = frag(xi, 4 * wk + a), a1 = frag(xi + kImage, 4 * wk + a), a2 = frag(xi + 2 * kImage, 4 * wk + a);
+      // corrections, smallest first: (2,0) (0,2) (1,1) ~ 2^-16, (1,0) (0,1) ~ 2^-8; then the leading product
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a2, b0[b], acl[a][b]);
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a0, b2[b], acl[a][b]);
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a1, b1[b], acl[a][b]);
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a1, b0[b], acl[a][b]);
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a0, b1[b], acl[a][b]);
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[a][b] = mma32(a0, b0[b], acc[a][b]);
+      split_col(a, rws);
+    }
+    store_img((u + 1) & 1);
+    if constexpr (decltype(lean)::value)
+      load_rows_lean(s + 1 + kPf, rws, prw);
+    else
+      load_rows(t1 + (int64_t)kPf * kStep, rws, prw);
+    __syncthreads();
+  };
   const int64_t n_steps = (t_end - t_begin + kStep - 1) / kStep;
-  for (int64_t s0 = 0; s0 < n_steps; s0 += kPf) {
+  // lean slices (make_plan: a prefix of the slices, the same for every tile): all steps but the last one or two run without
+  // clamps and masks - step s stages step s + 1 (a full step of this slice for s <= n_steps - 2) and requests the rows of step
+  // s + 1 + kPf and the indices of the step after it, all below m.  The general loop ends every slice: its last step stages
+  // nothing (all tokens at or beyond t_end: zeros) and clamps what it requests.
+  const int64_t s_lean = uniform64(slice < G.lean_slices ? ((n_steps - 1) / kPf) * kPf : 0);
+  for (int64_t s0 = 0; s0 < s_lean; s0 += kPf) {
+#pragma unroll
+    for (int u = 0; u < kPf; ++u) step(std::true_type{}, u, s0 + u);
+  }
+  for (int64_t s0 = s_lean; s0 < n_steps; s0 += kPf) {
 #pragma unroll
     for (int u = 0; u < kPf; ++u) {
-      const int64_t s = s0 + u;
-      if (s >= n_steps) break;
-      const int64_t t1 = t_begin + (s + 1) * kStep;
-      const unsigned char* dyi = lds + (u & 1) * kStage;       // dY parts (s0 is a multiple of kPf, kPf even: s & 1 == u & 1)
-      const unsigned char* xi = dyi + 3 * kImage;               // X parts
-      u32x4 b0[2], b1[2], b2[2];
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        b0[b] = frag(dyi, 2 * wn + b);
-        b1[b] = frag(dyi + kImage, 2 * wn + b);
-        b2[b] = frag(dyi + 2 * kImage, 2 * wn + b);
-      }
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const u32x4 a0 = frag(xi, 4 * wk + a), a1 = frag(xi + kImage, 4 * wk + a), a2 = frag(xi + 2 * kImage, 4 * wk + a);
-        // corrections, smallest first: (2,0) (0,2) (1,1) ~ 2^-16, (1,0) (0,1) ~ 2^-8; then the leading product
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a2, b0[b], acl[a][b]);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a0, b2[b], acl[a][b]);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a1, b1[b], acl[a][b]);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a1, b0[b], acl[a][b]);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acl[a][b] = mma32(a0, b1[b], acl[a][b]);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = mma32(a0, b0[b], acc[a][b]);
-        split_col(a, t1, rows[(u + 1) % kPf], prow[(u + 1) % kPf]);
-      }
-      store_img((u + 1) & 1);
-      load_rows(t1 + (int64_t)kPf * kStep, rows[(u + 1) % kPf], prow[(u + 1) % kPf]);
-      __syncthreads();
+      if (s0 + u >= n_steps) break;
+      step(std::false_type{}, u, s0 + u);
     }
   }
 #pragma unroll
@@ -417,6 +505,16 @@ bool make_plan(const sst_wgrad_problem_f32* pr, int n, x6_plan* plan) {
   while (slices > 8 && slices > max_slices) slices -= 8;
   G.slices = slices;
   G.tokens_per_slice = sst_align_up(sst_div_up(m, (int64_t)slices), (int64_t)kStep);
+  // lean slices (wgrad_x6_k): every step of the slice is full and every row the workgroup requests is inside [0, m) - the rows
+  // up to kPf steps and the positional indices one step further beyond the last step of the slice - so slice k is lean when
+  // (k + 1) tokens_per_slice + (kPf + 2) 32 <= m: a prefix of the slices.  None when a slice has fewer than three steps (the
+  // general loop ends every slice with its last one or two) or when a row stride leaves the 32-bit lane offsets of the loop.
+  int64_t lean = (m - (int64_t)(kPf + 2) * kStep) / G.tokens_per_slice;
+  lean = lean < 0 ? 0 : (lean > slices ? slices : lean);
+  if (G.tokens_per_slice < 3 * kStep) lean = 0;
+  for (int i = 0; i < n; ++i)
+    if (pr[i].ld_dy < 0 || pr[i].ld_x < 0 || pr[i].ld_dy >= (1 << 24) || pr[i].ld_x >= (1 << 24)) lean = 0;
+  G.lean_slices = (int)lean;
   plan->part_bytes = sst_align_up((int64_t)tiles * slices * kTile * kTile * 4, 256);
   plan->db_bytes = sst_align_up((int64_t)(db_cols > 0 ? db_cols : 1) * slices * 4, 256);
   return true;
@@ -430,6 +528,17 @@ int64_t sst_weight_grad_group_f32x6_workspace_bytes(const sst_wgrad_problem_f32*
   x6_plan plan;
   if (!make_plan(problems, n, &plan)) return SST_ERR_UNSUPPORTED;
   return plan.part_bytes + plan.db_bytes;
+}
+
+int sst_weight_grad_group_f32x6_plan(const sst_wgrad_problem_f32* problems, int n, int* tiles, int* slices,
+                                     int64_t* tokens_per_slice, int* lean_slices) {
+  x6_plan plan;
+  if (!make_plan(problems, n, &plan)) return SST_ERR_UNSUPPORTED;
+  if (tiles) *tiles = plan.g.tiles;
+  if (slices) *slices = plan.g.slices;
+  if (tokens_per_slice) *tokens_per_slice = plan.g.tokens_per_slice;
+  if (lean_slices) *lean_slices = plan.g.lean_slices;
+  return SST_OK;
 }
 
 }  // extern "C"
