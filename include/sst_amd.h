@@ -1444,6 +1444,102 @@ int sst_center_decode_f32(const int64_t* d_inds, const float* d_scores, int batc
                           float score_threshold, const float* post_center_range, float* d_boxes, uint8_t* d_keep,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training and decoding side of the FSD cluster heads, SparseClusterHeadV2 and FSDV2Head (csrc/cluster_head.hip).  fp32 data,
+ * everything on `stream`, no float atomics, no host read-back, bit-reproducible.
+ *
+ * Targets - replaces, for ALL tasks and ALL samples in one launch, the per-task per-sample Python loop of
+ * mmdet3d/models/dense_heads/sparse_cluster_head_v2.py:299-405 (modify_gt_for_single_task(_single_sample), get_targets,
+ * get_targets_single), fsd_v2_head.py:277-395 (the same, with xyz_for_assign of centroid_assign), sparse_cluster_head.py:269-289
+ * (split_by_batch / combine_by_batch) and :364-397 (assign_single), LiDARInstance3DBoxes.enlarged_box
+ * (core/bbox/structures/lidar_box3d.py:269-285) and BasePointBBoxCoder.encode (core/bbox/coders/base_point_bbox_coder.py:36-58).
+ *   d_xyz_assign, d_xyz_base [n, 3] fp32: the points tested for membership and the points the regression is relative to (the
+ *   same pointer unless centroid_assign).  Row i belongs to sample d_batch_idx[i * batch_idx_stride] (int64; rows of different
+ *   samples may interleave; an index outside [0, batch) gives a background row).  d_boxes [n_boxes, box_cols] fp32, box_cols 7,
+ *   9 or 10: (x, y, z_bottom, w, l, h, rz [, vx, vy [, copy-paste flag]]), d_box_labels int64, sample s = boxes
+ *   d_box_offsets[s] .. d_box_offsets[s + 1] (device int32 [batch + 1]).  class_table: HOST int32 [n_classes][2] = (task or -1,
+ *   class index within the task), n_classes <= 64; task_classes: HOST int32 [n_tasks], n_tasks <= SST_CLUSTER_MAX_TASKS, at most
+ *   32 classes each.  A box with label < 0, >= n_classes or of a class in no task is in no list.  Membership: dpp_box /
+ *   dpp_classify of csrc/pib_test.h != 0 on the box enlarged by has_enlarge_width ? enlarge_width : nothing (w, l, h +=
+ *   (float)(2 width), z -= (float)width; for a negative width a box whose enlarged w, l or h would be <= 0 keeps its own
+ *   extents).  Per task the assigned box is the hit with the smallest (class index within the task, box index): the first
+ *   hit of the reference's class-regrouped list.
+ *   d_out: one allocation of sst_cluster_targets_layout(n, n_tasks, code_size, offsets) bytes; the call fills HOST
+ *   offsets[4 * n_tasks] with the byte offsets (multiples of 256) of each task's labels int64 [n] (class index within the task,
+ *   or the task's class count for background), bbox_targets fp32 [n, code_size] (box xyz - base, each one rounded subtraction;
+ *   logf(dim + 1e-6f); sinf / cosf of rz; vx, vy when code_size is 10), bbox_weights fp32 [n, code_size] (1 on positive rows, the
+ *   last two columns = box column 9 when box_cols is 10: sparse_cluster_head_v2.py:393-398) and assigned int32 [n] (index into
+ *   d_boxes or -1).  Rows without a hit are zero.  code_size 8 goes with 7 box columns, 10 with 9 or 10 (SST_ERR_ARG otherwise).
+ *   sst_cluster_targets_box_tile(): boxes per LDS tile.
+ *   sst_cluster_encode_f32: BasePointBBoxCoder.encode on n boxes and n base points.
+ *
+ * Losses of all tasks - replaces loss_single_task (sparse_cluster_head_v2.py:192-297, fsd_v2_head.py:168-275) per task:
+ * FocalLoss (sigmoid; py_sigmoid_focal_loss of mmdet3d/models/losses/focal_loss.py:13-67, sum / avg_factor), the nonzero() of
+ * pos_inds, the three or four gathered L1Loss calls, and autograd's backward.  tasks: HOST array of n_tasks
+ * sst_cluster_loss_task (device pointers: logits [n, classes], reg_preds / bbox_targets / bbox_weights [n, code_size], labels
+ * int64 [n]; d_logits / d_reg_preds: the backward's outputs), n >= 1, classes <= 32.  code_weight: HOST float [code_size] or NULL;
+ * loss_weights: HOST float [5] (cls, center, size, rot, vel); smooth_l1_beta: HOST float [5] in the same order or NULL - a
+ * regression loss with beta > 0 is mmdet's SmoothL1Loss (0.5 d^2 / beta below beta, |d| - 0.5 beta above; configs/fsdv2/
+ * fsdv2_argo_2x.py), with 0 its L1Loss ([0] is not read).  Positive rows: 0 <= label < classes; label == classes:
+ * background (all-zero targets).
+ *   loss_cls = w_cls * sum(focal) / cls_avg;  loss_center / size / rot = w * sum(|pred - target| weight code_weight over columns
+ *   0-2 / 3-5 / 6-7 of the positive rows) / reg_avg;  loss_vel = w_vel * sum(columns 8-9) / (2 num_pos) (the reference gives
+ *   loss_vel no avg_factor: the mean over elements).  The four regression losses are exactly 0 without a positive row.
+ *   d_out float [n_tasks][5]; d_counts double [n_tasks][4] = (num_pos, status, cls_avg, reg_avg).  status bit 0: a label outside
+ *   [0, classes] - the row contributes nothing; bit 1: a weight of column 8 / 9 of a positive row other than 0 or 1.
+ *   Forward, phases = SST_CLUSTER_LOSS_COUNTS | SST_CLUSTER_LOSS_FINISH: a launch (grid = sst_cluster_loss_tile_rows() row
+ *   tiles x tasks) writing one record per workgroup into d_workspace (sst_cluster_loss_workspace_bytes(n, n_tasks)) and a
+ *   one-workgroup launch that adds the records in index order, writes d_counts with cls_avg = n, reg_avg = num_pos and the
+ *   losses.  With phases = COUNTS alone the second launch only writes d_counts; with FINISH alone it reads cls_avg / reg_avg
+ *   FROM d_counts - so a caller can average the factors over processes on the device between the two calls (reduce_mean).
+ *   Sums are carried in fp64 from the lane on.  Backward = one launch (grid = 256-row tiles x tasks): d_g float [n_tasks][5]
+ *   (device: upstream gradients) and the forward's d_counts -> every element of every task's d_logits and d_reg_preds;
+ *   recomputed from the logits; the L1 gradient is sign(pred - target) weight code_weight w / avg, sign(0) = 0
+ *   ((pred - target) / beta in its place below a SmoothL1Loss's beta).
+ *
+ * Decoding of one task - BasePointBBoxCoder.decode (base_point_bbox_coder.py:60-82): d_boxes [n, code_size - 1] = (base + d,
+ * expf(dims) - 1e-6f, atan2f(sin, cos) [, vx, vy]); optionally d_scores [n, classes + 1] = sigmoid(d_logits [n, classes]) with a
+ * zero last column (sparse_cluster_head_v2.py:534, :552-554) and d_bev [n, 5] = (x - w / 2, y - l / 2, x + w / 2, y + l / 2, yaw),
+ * the rows xywhr2xyxyr(boxes.bev) gives for the NMS.
+ *
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer, a bad size or table; SST_ERR_UNSUPPORTED for a count
+ * beyond the limits above.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_CLUSTER_MAX_TASKS 8
+#define SST_CLUSTER_LOSS_COUNTS 1
+#define SST_CLUSTER_LOSS_FINISH 2
+typedef struct sst_cluster_loss_task {
+  const float* logits;
+  const float* reg_preds;
+  const int64_t* labels;
+  const float* bbox_targets;
+  const float* bbox_weights;
+  float* d_logits;
+  float* d_reg_preds;
+  int32_t classes;
+  int32_t reserved;
+} sst_cluster_loss_task;
+int sst_cluster_max_tasks(void);
+int sst_cluster_targets_box_tile(void);
+int sst_cluster_loss_tile_rows(void);
+int64_t sst_cluster_targets_layout(int64_t n, int n_tasks, int code_size, int64_t* offsets);
+int sst_cluster_targets_f32(const float* d_xyz_assign, const float* d_xyz_base, int64_t n, const int64_t* d_batch_idx,
+                            int64_t batch_idx_stride, int batch, const float* d_boxes, int box_cols,
+                            const int64_t* d_box_labels, const int32_t* d_box_offsets, int64_t n_boxes,
+                            const int32_t* class_table, int n_classes, const int32_t* task_classes, int n_tasks, int code_size,
+                            int has_enlarge_width, double enlarge_width, void* d_out, void* stream);
+int sst_cluster_encode_f32(const float* d_boxes, int box_cols, const float* d_base, int64_t n, int code_size, float* d_out,
+                           void* stream);
+int64_t sst_cluster_loss_workspace_bytes(int64_t n, int n_tasks);
+int sst_cluster_loss_fwd_f32(const sst_cluster_loss_task* tasks, int n_tasks, int64_t n, int code_size, float gamma, float alpha,
+                             const float* code_weight, const float* loss_weights, const float* smooth_l1_beta, int phases,
+                             float* d_out, double* d_counts, void* d_workspace, void* stream);
+int sst_cluster_loss_bwd_f32(const sst_cluster_loss_task* tasks, int n_tasks, int64_t n, int code_size, float gamma, float alpha,
+                             const float* code_weight, const float* loss_weights, const float* smooth_l1_beta, const float* d_g,
+                             const double* d_counts, void* stream);
+int sst_cluster_decode_f32(const float* d_reg_preds, const float* d_base, const float* d_logits, int64_t n, int code_size,
+                           int classes, float* d_boxes, float* d_scores, float* d_bev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

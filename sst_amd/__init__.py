@@ -44,6 +44,9 @@ from .detectors import (DETECTORS, HEADS, NECKS, FSD, FSDV2, DynamicCenterPoint,
 from . import center_head  # noqa: F401
 from .center_head import (BBOX_CODERS, CenterHead, CenterPointBBoxCoder, build_bbox_coder, center_decode, center_loss,  # noqa: F401
                           center_targets)
+from . import cluster_head  # noqa: F401
+from .cluster_head import (BasePointBBoxCoder, FSDSeparateHead, FSDV2Head, SparseClusterHeadV2, cluster_decode, cluster_encode,  # noqa: F401
+                           cluster_loss, cluster_targets)
 
 __version__ = '0.1.0'
 
@@ -71,4 +74,6 @@ __all__ = [
     'seg_loss', 'seg_point_targets', 'seg_vote_loss',
     'center_head', 'center_targets', 'center_loss', 'center_decode', 'CenterHead', 'CenterPointBBoxCoder', 'BBOX_CODERS',
     'build_bbox_coder',
+    'cluster_head', 'cluster_targets', 'cluster_loss', 'cluster_decode', 'cluster_encode', 'BasePointBBoxCoder', 'FSDSeparateHead',
+    'SparseClusterHeadV2', 'FSDV2Head',
 ]

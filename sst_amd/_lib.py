@@ -36,6 +36,12 @@ class CastProblemBF16(ctypes.Structure):
                 ('transpose', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class ClusterLossTask(ctypes.Structure):
+    """sst_cluster_loss_task of include/sst_amd.h"""
+    _fields_ = [('logits', c_ptr), ('reg_preds', c_ptr), ('labels', c_ptr), ('bbox_targets', c_ptr), ('bbox_weights', c_ptr),
+                ('d_logits', c_ptr), ('d_reg_preds', c_ptr), ('classes', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 class WgradProblemF32(ctypes.Structure):
     """sst_wgrad_problem_f32 of include/sst_amd.h"""
     _fields_ = [('dy', c_ptr), ('x', c_ptr), ('m', c_i64), ('ld_dy', c_i64), ('ld_x', c_i64), ('dw', c_ptr), ('db', c_ptr),
@@ -359,6 +365,18 @@ _SIGNATURES = {
                                         c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_center_decode_f32': (c_i32, [c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_i32, c_i32,
                                       c_f32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_cluster_max_tasks': (c_i32, []),
+    'sst_cluster_targets_box_tile': (c_i32, []),
+    'sst_cluster_loss_tile_rows': (c_i32, []),
+    'sst_cluster_targets_layout': (c_i64, [c_i64, c_i32, c_i32, c_ptr]),
+    'sst_cluster_targets_f32': (c_i32, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_i32,
+                                        c_ptr, c_i32, c_i32, c_i32, ctypes.c_double, c_ptr, c_ptr]),
+    'sst_cluster_encode_f32': (c_i32, [c_ptr, c_i32, c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
+    'sst_cluster_loss_workspace_bytes': (c_i64, [c_i64, c_i32]),
+    'sst_cluster_loss_fwd_f32': (c_i32, [c_ptr, c_i32, c_i64, c_i32, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_i32, c_ptr, c_ptr,
+                                         c_ptr, c_ptr]),
+    'sst_cluster_loss_bwd_f32': (c_i32, [c_ptr, c_i32, c_i64, c_i32, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_cluster_decode_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
