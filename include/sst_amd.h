@@ -1540,6 +1540,134 @@ int sst_cluster_loss_bwd_f32(const sst_cluster_loss_task* tasks, int n_tasks, in
 int sst_cluster_decode_f32(const float* d_reg_preds, const float* d_base, const float* d_logits, int64_t n, int code_size,
                            int classes, float* d_boxes, float* d_scores, float* d_bev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The second stage of FSD / FSDv2 around its network, GroupCorrectionHead with FullySparseBboxHead (csrc/roi_head.hip).  fp32
+ * data, everything on `stream`, no float atomics, no host read-back, bit-reproducible.  Boxes are (x, y, z_bottom, w, l, h, rz
+ * [, vx, vy]); proposals have 7 or 9 columns, ground truth 7 or more (the first 7 are read).  Sample s owns proposals
+ * prop_offsets[s] .. prop_offsets[s + 1] and boxes gt_offsets[s] .. gt_offsets[s + 1] (device int32 [batch + 1]).
+ *
+ * sst_roi_assign_f32 - replaces, for ALL samples and classes in one launch, the loop of mmdet3d/models/roi_heads/
+ * fsd_roi_head.py:229-289 (_assign_and_sample: per sample and class two boolean compactions and an IoU launch) and
+ * BboxOverlaps3D / BaseInstance3DBoxes.overlaps (core/bbox/structures/base_box3d.py:395-450).  Per proposal (one lane each,
+ * sst_roi_assign_block() per workgroup, the sample's boxes through LDS tiles of sst_roi_assign_gt_tile()): the 3-D IoU with the
+ * boxes of its sample and, when class_mask != 0 (the list of per-class assigners), of its own predicted class - the BEV overlap
+ * of csrc/bev_clip.h x the clamped height overlap / the clamped union, the operation order of box_ops.boxes3d_overlaps_lidar.
+ * A box with a label outside [0, num_classes) and a proposal with such a label match nothing.
+ *   iou fp32 [n_props, ld]: column j = box gt_offsets[s] + j of the proposal's sample, -1 where masked or past the sample's
+ *   boxes (every element is written); ld >= the largest box count of a sample.  max_iou fp32 [n_props]: the row maximum, 0
+ *   without a match; argmax int32 [n_props]: the first box (index into gts) that attains it, -1 without a match.
+ *
+ * sst_roi_sample_targets_f32 - one launch, one workgroup per sample; replaces mmdet's MaxIoUAssigner.assign_wrt_overlaps (the
+ * Python loop over boxes of gt_max_assign_all), core/bbox/samplers/iou_neg_piecewise_sampler.py:46-164 (nonzero, randperm,
+ * unique) and bbox_heads/fsd_bbox_head.py:343-543 (get_targets, _get_target_single, get_multi_class_soft_label) with
+ * core/bbox/coders/delta_xyzwhlr_bbox_coder.py:20-56 (encode).  Thresholds are indexed by the proposal's (box's) class when
+ * class_mask != 0, else [0].
+ *   Assignment: background where 0 <= max < neg_iou_thr, positive (argmax) where max >= pos_iou_thr, ignored between; then for
+ *   every box in index order whose column maximum is >= min_pos_iou, every proposal whose IoU equals that maximum goes to it
+ *   (the last box wins).  Sampling: min(positives, num_expected_pos) positives; num - that many negatives: all when there are
+ *   no more, else piece k = [piece_thr[k + 1], piece_thr[k]) (the last from 0) takes (int)(expected * piece_frac[k]) + the
+ *   shortfall carried from the pieces before it (the last piece: what is left).  "k of a pool" = its k smallest (keys[i], i).
+ *   Outputs per sample, num rows each, positives first, each group in ascending proposal index, zero / -1 padding:
+ *   rois fp32 [batch * num, 1 + prop_cols] = (sample, box), src int32 (proposal index), gt_index int32 (index into gts, -1 off
+ *   the positives), labels int64 (-1 off the positives), iou_out fp32 (row maximum), soft_label fp32 (get_multi_class_soft_label
+ *   on cls_pos_thr / cls_neg_thr of the box's class; 0 on negatives), reg_mask uint8, targets fp32 [batch * num, 7]
+ *   (_get_target_single; 0 off the positives), counts int32 [batch, 2] = (positives, negatives), (-1, -1) for a sample with
+ *   more than sst_roi_sample_max_proposals() proposals (SST_ERR_UNSUPPORTED when max_props_per_sample says so up front).
+ *   assigned: int32 [n_props] workspace (-1 background, -2 ignored, else the box).  Every element is written.
+ *
+ * sst_roi_loss_fwd_f32 / _bwd_f32 - replaces FullySparseBboxHead.loss, filter_pos_assigned_but_empty_rois and
+ * get_corner_loss_lidar (fsd_bbox_head.py:207-341, :546-579) over n >= 1 RoI rows:
+ *   loss_cls = w_cls * sum over nonempty rows of BCE-with-logits(cls_score, soft_label) / cls_avg;
+ *   loss_bbox = w_reg * sum over rows with reg_mask & nonempty of loss(bbox_pred - targets) * code_weight / reg_avg, loss = |d|
+ *   (beta == 0) or mmdet's smooth L1;  loss_corner = w_corner * mean over 8 corners x the kept rows of Huber(min(distance to the
+ *   box's corners, to the corners of the box turned by pi)) of the prediction decoded against the zero-centred RoI, turned by
+ *   roi_ry + pi / 2 and moved to the RoI centre; kept rows = those of loss_bbox with labels == car_index (all when car_index < 0);
+ *   with_corner == 0: no corner loss.  loss_bbox and loss_corner are exactly 0 without a row.
+ *   d_out float [5] = (loss_cls, loss_bbox, loss_corner, num_pos_rois, num_neg_rois); d_counts double [4] = (num_pos, corner
+ *   rows, cls_avg = n, reg_avg = num_pos).  phases: SST_ROI_LOSS_COUNTS | SST_ROI_LOSS_FINISH as for sst_cluster_loss_fwd_f32
+ *   (two launches; COUNTS alone stops after d_counts, FINISH alone reads the averaging factors from d_counts).  Workspace:
+ *   sst_roi_loss_workspace_bytes(n).  Sums are fp64 from the lane on, in a fixed order.
+ *   Backward, one launch: d_g float [3] (device; upstream gradients of the three losses) and d_counts -> every element of
+ *   d_dcls [n] and d_dbbox [n, 7], with the corner loss's gradient through the decode derived by hand.
+ *
+ * sst_roi_decode_f32 - fsd_bbox_head.py:609, :634-653: d_boxes [n, roi_cols - 1] = decode_from_rois (velocity columns of a
+ * 9-column RoI pass through), d_scores [n] = sigmoid(d_cls_score) (optional), d_bev [n, 5] = the xyxyr NMS rows (optional).
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_ROI_MAX_CLASSES 16
+#define SST_ROI_MAX_PIECES 8
+#define SST_ROI_LOSS_COUNTS 1
+#define SST_ROI_LOSS_FINISH 2
+typedef struct sst_roi_assign_args {
+  const float* props;
+  const int64_t* prop_labels;
+  const int32_t* prop_offsets;
+  const float* gts;
+  const int64_t* gt_labels;
+  const int32_t* gt_offsets;
+  float* iou;
+  float* max_iou;
+  int32_t* argmax;
+  int64_t n_props, n_gts, ld;
+  int32_t prop_cols, gt_cols, batch, num_classes, class_mask, reserved;
+} sst_roi_assign_args;
+typedef struct sst_roi_sample_args {
+  const float* props;
+  const int64_t* prop_labels;
+  const int32_t* prop_offsets;
+  const float* gts;
+  const int64_t* gt_labels;
+  const int32_t* gt_offsets;
+  const float* iou;
+  const float* max_iou;
+  const int32_t* argmax;
+  const float* keys;
+  int32_t* assigned;
+  float* rois;
+  int32_t* src;
+  int32_t* gt_index;
+  int64_t* labels;
+  float* iou_out;
+  float* soft_label;
+  uint8_t* reg_mask;
+  float* targets;
+  int32_t* counts;
+  int64_t n_props, n_gts, ld, max_props_per_sample;
+  int32_t prop_cols, gt_cols, batch, num_classes, class_mask, num, num_expected_pos, n_pieces;
+  float pos_iou_thr[SST_ROI_MAX_CLASSES], neg_iou_thr[SST_ROI_MAX_CLASSES], min_pos_iou[SST_ROI_MAX_CLASSES];
+  float piece_thr[SST_ROI_MAX_PIECES];
+  double cls_pos_thr[SST_ROI_MAX_CLASSES], cls_neg_thr[SST_ROI_MAX_CLASSES];
+  double piece_frac[SST_ROI_MAX_PIECES];
+} sst_roi_sample_args;
+typedef struct sst_roi_loss_args {
+  const float* cls_score;
+  const float* bbox_pred;
+  const uint8_t* nonempty;
+  const float* rois;
+  const float* soft_label;
+  const uint8_t* reg_mask;
+  const float* targets;
+  const int32_t* gt_index;
+  const int64_t* labels;
+  const float* gts;
+  int64_t n, n_gts;
+  int32_t roi_cols, gt_cols, with_corner, car_index;
+  float beta, w_cls, w_reg, w_corner;
+  float code_weight[7];
+  float reserved;
+} sst_roi_loss_args;
+int sst_roi_assign_gt_tile(void);
+int sst_roi_assign_block(void);
+int sst_roi_sample_max_proposals(void);
+int sst_roi_assign_f32(const sst_roi_assign_args* args, void* stream);
+int sst_roi_sample_targets_f32(const sst_roi_sample_args* args, void* stream);
+int64_t sst_roi_loss_workspace_bytes(int64_t n);
+int sst_roi_loss_fwd_f32(const sst_roi_loss_args* args, int phases, float* d_out, double* d_counts, void* d_workspace,
+                         void* stream);
+int sst_roi_loss_bwd_f32(const sst_roi_loss_args* args, const float* d_g, const double* d_counts, float* d_dcls, float* d_dbbox,
+                         void* stream);
+int sst_roi_decode_f32(const float* d_rois, int roi_cols, const float* d_bbox_pred, const float* d_cls_score, int64_t n,
+                       float* d_boxes, float* d_scores, float* d_bev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

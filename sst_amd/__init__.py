@@ -47,6 +47,9 @@ from .center_head import (BBOX_CODERS, CenterHead, CenterPointBBoxCoder, build_b
 from . import cluster_head  # noqa: F401
 from .cluster_head import (BasePointBBoxCoder, FSDSeparateHead, FSDV2Head, SparseClusterHeadV2, cluster_decode, cluster_encode,  # noqa: F401
                            cluster_loss, cluster_targets)
+from . import roi_head  # noqa: F401
+from .roi_head import (DeltaXYZWLHRBBoxCoder, FullySparseBboxHead, GroupCorrectionHead, roi_assign_sample, roi_compact,  # noqa: F401
+                       roi_decode, roi_loss)
 
 __version__ = '0.1.0'
 
@@ -76,4 +79,6 @@ __all__ = [
     'build_bbox_coder',
     'cluster_head', 'cluster_targets', 'cluster_loss', 'cluster_decode', 'cluster_encode', 'BasePointBBoxCoder', 'FSDSeparateHead',
     'SparseClusterHeadV2', 'FSDV2Head',
+    'roi_head', 'roi_assign_sample', 'roi_compact', 'roi_loss', 'roi_decode', 'DeltaXYZWLHRBBoxCoder', 'FullySparseBboxHead',
+    'GroupCorrectionHead',
 ]

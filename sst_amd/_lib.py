@@ -52,6 +52,30 @@ def _struct(name, doc, fields):
     return type(name, (ctypes.Structure,), {'__doc__': doc, '_fields_': fields})
 
 
+_I32 = ctypes.c_int32
+RoiAssignArgs = _struct('RoiAssignArgs', 'sst_roi_assign_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('props', 'prop_labels', 'prop_offsets', 'gts', 'gt_labels', 'gt_offsets', 'iou', 'max_iou',
+                                    'argmax')]
+    + [(k, c_i64) for k in ('n_props', 'n_gts', 'ld')]
+    + [(k, _I32) for k in ('prop_cols', 'gt_cols', 'batch', 'num_classes', 'class_mask', 'reserved')]))
+RoiSampleArgs = _struct('RoiSampleArgs', 'sst_roi_sample_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('props', 'prop_labels', 'prop_offsets', 'gts', 'gt_labels', 'gt_offsets', 'iou', 'max_iou',
+                                    'argmax', 'keys', 'assigned', 'rois', 'src', 'gt_index', 'labels', 'iou_out', 'soft_label',
+                                    'reg_mask', 'targets', 'counts')]
+    + [(k, c_i64) for k in ('n_props', 'n_gts', 'ld', 'max_props_per_sample')]
+    + [(k, _I32) for k in ('prop_cols', 'gt_cols', 'batch', 'num_classes', 'class_mask', 'num', 'num_expected_pos', 'n_pieces')]
+    + [(k, ctypes.c_float * 16) for k in ('pos_iou_thr', 'neg_iou_thr', 'min_pos_iou')]
+    + [('piece_thr', ctypes.c_float * 8)]
+    + [(k, ctypes.c_double * 16) for k in ('cls_pos_thr', 'cls_neg_thr')]
+    + [('piece_frac', ctypes.c_double * 8)]))
+RoiLossArgs = _struct('RoiLossArgs', 'sst_roi_loss_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('cls_score', 'bbox_pred', 'nonempty', 'rois', 'soft_label', 'reg_mask', 'targets',
+                                    'gt_index', 'labels', 'gts')]
+    + [(k, c_i64) for k in ('n', 'n_gts')]
+    + [(k, _I32) for k in ('roi_cols', 'gt_cols', 'with_corner', 'car_index')]
+    + [(k, ctypes.c_float) for k in ('beta', 'w_cls', 'w_reg', 'w_corner')]
+    + [('code_weight', ctypes.c_float * 7), ('reserved', ctypes.c_float)]))
+
 _P = ctypes.c_void_p
 EncoderLayerFwdArgs = _struct('EncoderLayerFwdArgs', 'sst_encoder_layer_fwd_args of include/sst_amd.h', (
     [('m', c_i64), ('n_windows', c_i64)] + [(k, ctypes.c_int32) for k in ('n_heads', 'act', 'max_tokens', 'impl')]
@@ -377,6 +401,15 @@ _SIGNATURES = {
                                          c_ptr, c_ptr]),
     'sst_cluster_loss_bwd_f32': (c_i32, [c_ptr, c_i32, c_i64, c_i32, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_cluster_decode_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_roi_assign_gt_tile': (c_i32, []),
+    'sst_roi_assign_block': (c_i32, []),
+    'sst_roi_sample_max_proposals': (c_i32, []),
+    'sst_roi_assign_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_roi_sample_targets_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_roi_loss_workspace_bytes': (c_i64, [c_i64]),
+    'sst_roi_loss_fwd_f32': (c_i32, [c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_roi_loss_bwd_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_roi_decode_f32': (c_i32, [c_ptr, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -202,8 +202,11 @@ def boxes3d_overlaps_lidar(boxes1, boxes2, mode='iou'):
     overlaps_bev = boxes_overlap_bev(xywhr2xyxyr(lidar_bev(boxes1)).contiguous(),
                                      xywhr2xyxyr(lidar_bev(boxes2)).contiguous())
     overlaps_3d = overlaps_bev * overlaps_h
-    volume1 = boxes1[:, 3:6].prod(dim=1).view(-1, 1)
-    volume2 = boxes2[:, 3:6].prod(dim=1).view(1, -1)
+    # BaseInstance3DBoxes.volume (base_box3d.py:69-72): (w * l) * h, one rounding per product.  prod(dim=1) multiplies in an order
+    # of the reduction kernel's choosing (one ulp apart on some boxes); the RoI head's assignment kernel (csrc/roi_head.hip) has
+    # to produce these values bit for bit
+    volume1 = (boxes1[:, 3] * boxes1[:, 4] * boxes1[:, 5]).view(-1, 1)
+    volume2 = (boxes2[:, 3] * boxes2[:, 4] * boxes2[:, 5]).view(1, -1)
     if mode == 'iou':
         return overlaps_3d / torch.clamp(volume1 + volume2 - overlaps_3d, min=1e-8)
     return overlaps_3d / torch.clamp(volume1, min=1e-8)
