@@ -1668,6 +1668,81 @@ int sst_roi_loss_bwd_f32(const sst_roi_loss_args* args, const float* d_g, const 
 int sst_roi_decode_f32(const float* d_rois, int roi_cols, const float* d_bbox_pred, const float* d_cls_score, int64_t n,
                        float* d_boxes, float* d_scores, float* d_bev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Anchor3DHead around its three 1 x 1 convolutions (csrc/anchor_head.hip).  fp32 data, everything on `stream`, no float atomics,
+ * no host read-back, bit-reproducible.  No anchor tensor is read: anchor a = ((h * W + w) * n_sizes + s) * n_rots + r of a sample
+ * (the reference's flattening of its [1, H, W, n_sizes, n_rots, 7] tensor) is (centers.x[s][w], centers.y[s][h], centers.z[s],
+ * sizes[s], rots[r]).  centers: device fp32, xs [n_sizes, W], then ys [n_sizes, H], then zs [n_sizes] - the generator's own
+ * torch.linspace tables, so every centre is bit-equal to the reference's.  Boxes are (x, y, z_bottom, w, l, h, rz, ...) with
+ * gt_cols >= 7 columns; sample b owns boxes gt_offsets[b] .. gt_offsets[b + 1] (device int32 [batch + 1]).
+ *
+ * sst_anchor_targets_f32 - one memset and two launches for all samples and sizes; replaces anchor_target_3d_single
+ * (mmdet3d/models/dense_heads/train_mixins.py:101-314) with a list of MaxIoUAssigner (one per size; pos_iou_thr / neg_iou_thr /
+ * min_pos_iou are host arrays [n_sizes], all > 0 but neg), BboxOverlapsNearest3D('lidar') (iou3d_calculator.py:94-140,
+ * nearest_bev of lidar_box3d.py:123-141, mmdet bbox_overlaps: every step one correctly rounded fp32 operation) and
+ * PseudoSampler.  The anchors of size s meet the sample's boxes - those with label s when assign_per_class.  Per anchor: the
+ * maximum IoU and its first arg-max; background where max < neg_iou_thr, the arg-max where max >= pos_iou_thr, ignored between;
+ * then for every box in index order whose largest IoU over the size's anchors is >= min_pos_iou, every anchor whose IoU equals
+ * it goes to the box (the last box wins).
+ *   d_assigned int32 [batch, H * W * n_sizes * n_rots]: the box index within the sample, -1 background, -2 ignored (every
+ *   element is written).  d_state int32 [n_sizes * n_gts + batch]: the float bits of the largest IoU per (size, box), then the
+ *   positives per sample.  A workgroup is a tile of sst_anchor_block() cells; the boxes pass through LDS in chunks of
+ *   sst_anchor_targets_gt_chunk().
+ *
+ * sst_anchor_loss_fwd_f32 / _bwd_f32 - replaces Anchor3DHead.loss / loss_single (dense_heads/anchor3d_head.py:197-379) with
+ * sigmoid FocalLoss, L1Loss (smooth_l1 == 0) or SmoothL1Loss(beta), softmax CrossEntropyLoss of the direction, all 'mean' with
+ * avg_factor = sum over samples of max(positives, 1).  cls_score [B, n_a * C, H, W], bbox_pred [B, n_a * 7, H, W], dir_pred
+ * [B, n_a * 2, H, W] or NULL (no direction classifier), n_a = n_sizes * n_rots: read where they lie.  The target of a positive
+ * anchor is formed in the kernel: DeltaXYZWLHRBBoxCoder.encode, get_direction_target(dir_offset), add_sin_difference when
+ * sin_diff.  The weight of a class term: 0 ignored, pos_weight (> 0) or 1 positive, 1 background.
+ *   Forward, two launches: d_out float [4] = (loss_cls, loss_bbox, loss_dir, avg_factor); workspace
+ *   sst_anchor_loss_workspace_bytes(batch, H, W).  Sums are fp64 from the lane on, in a fixed order.
+ *   Backward, one launch: d_g_* (device scalars, NULL = no upstream gradient) and d_out -> every element of the three gradient
+ *   maps, zeros included.
+ *
+ * sst_anchor_decode_f32 - one sample: get_bboxes_single :465-530 after its topk.  d_inds int64 [n] anchor indices (NULL: 0 ..
+ * n - 1); d_boxes [n, 7] = DeltaXYZWLHRBBoxCoder.decode against the analytic anchor, d_scores [n, C + 1] = sigmoid with the zero
+ * background column, d_dir int64 [n] = the direction arg-max (0 at a tie, 0 without dir_pred), d_bev [n, 5] = xyxyr NMS rows.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_ANCHOR_MAX_SIZES 8
+#define SST_ANCHOR_MAX_ROTS 4
+typedef struct sst_anchor_grid {
+  const float* centers;
+  int32_t H, W, n_sizes, n_rots;
+  float sizes[SST_ANCHOR_MAX_SIZES][3];
+  float rots[SST_ANCHOR_MAX_ROTS];
+} sst_anchor_grid;
+typedef struct sst_anchor_loss_args {
+  const float* cls_score;
+  const float* bbox_pred;
+  const float* dir_pred;
+  const int32_t* assigned;
+  const float* gts;
+  const int64_t* gt_labels;
+  const int32_t* gt_offsets;
+  const int32_t* pos_counts;
+  int64_t n_gts;
+  int32_t gt_cols, batch, num_classes, smooth_l1, sin_diff, reserved;
+  float gamma, alpha, w_cls, w_bbox, w_dir, beta, pos_weight, dir_offset;
+  float code_weight[7];
+  float reserved_f;
+} sst_anchor_loss_args;
+int sst_anchor_targets_gt_chunk(void);
+int sst_anchor_block(void);
+int sst_anchor_targets_f32(const sst_anchor_grid* grid, const float* d_gts, int gt_cols, const int64_t* d_gt_labels,
+                           const int32_t* d_gt_offsets, int64_t n_gts, int batch, int assign_per_class, const float* pos_iou_thr,
+                           const float* neg_iou_thr, const float* min_pos_iou, int32_t* d_assigned, int32_t* d_state,
+                           void* stream);
+int64_t sst_anchor_loss_workspace_bytes(int batch, int grid_h, int grid_w);
+int sst_anchor_loss_fwd_f32(const sst_anchor_grid* grid, const sst_anchor_loss_args* args, float* d_out, void* d_workspace,
+                            void* stream);
+int sst_anchor_loss_bwd_f32(const sst_anchor_grid* grid, const sst_anchor_loss_args* args, const float* d_out,
+                            const float* d_g_cls, const float* d_g_bbox, const float* d_g_dir, float* d_dcls, float* d_dbbox,
+                            float* d_ddir, void* stream);
+int sst_anchor_decode_f32(const sst_anchor_grid* grid, const float* d_cls_score, const float* d_bbox_pred,
+                          const float* d_dir_pred, const int64_t* d_inds, int64_t n, int num_classes, float* d_boxes,
+                          float* d_scores, int64_t* d_dir, float* d_bev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,9 @@ from .cluster_head import (BasePointBBoxCoder, FSDSeparateHead, FSDV2Head, Spars
 from . import roi_head  # noqa: F401
 from .roi_head import (DeltaXYZWLHRBBoxCoder, FullySparseBboxHead, GroupCorrectionHead, roi_assign_sample, roi_compact,  # noqa: F401
                        roi_decode, roi_loss)
+from . import anchor_head  # noqa: F401
+from .anchor_head import (ANCHOR_GENERATORS, SECONDFPN, AlignedAnchor3DRangeGenerator, Anchor3DHead, Anchor3DRangeGenerator,  # noqa: F401
+                          anchor_decode, anchor_loss, anchor_targets, build_anchor_generator)
 
 __version__ = '0.1.0'
 
@@ -81,4 +84,6 @@ __all__ = [
     'SparseClusterHeadV2', 'FSDV2Head',
     'roi_head', 'roi_assign_sample', 'roi_compact', 'roi_loss', 'roi_decode', 'DeltaXYZWLHRBBoxCoder', 'FullySparseBboxHead',
     'GroupCorrectionHead',
+    'anchor_head', 'anchor_targets', 'anchor_loss', 'anchor_decode', 'Anchor3DHead', 'SECONDFPN', 'ANCHOR_GENERATORS',
+    'Anchor3DRangeGenerator', 'AlignedAnchor3DRangeGenerator', 'build_anchor_generator',
 ]

@@ -76,6 +76,17 @@ RoiLossArgs = _struct('RoiLossArgs', 'sst_roi_loss_args of include/sst_amd.h', (
     + [(k, ctypes.c_float) for k in ('beta', 'w_cls', 'w_reg', 'w_corner')]
     + [('code_weight', ctypes.c_float * 7), ('reserved', ctypes.c_float)]))
 
+AnchorGrid = _struct('AnchorGrid', 'sst_anchor_grid of include/sst_amd.h', (
+    [('centers', ctypes.c_void_p)] + [(k, _I32) for k in ('H', 'W', 'n_sizes', 'n_rots')]
+    + [('sizes', ctypes.c_float * 3 * 8), ('rots', ctypes.c_float * 4)]))
+AnchorLossArgs = _struct('AnchorLossArgs', 'sst_anchor_loss_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('cls_score', 'bbox_pred', 'dir_pred', 'assigned', 'gts', 'gt_labels', 'gt_offsets',
+                                    'pos_counts')]
+    + [('n_gts', c_i64)]
+    + [(k, _I32) for k in ('gt_cols', 'batch', 'num_classes', 'smooth_l1', 'sin_diff', 'reserved')]
+    + [(k, ctypes.c_float) for k in ('gamma', 'alpha', 'w_cls', 'w_bbox', 'w_dir', 'beta', 'pos_weight', 'dir_offset')]
+    + [('code_weight', ctypes.c_float * 7), ('reserved_f', ctypes.c_float)]))
+
 _P = ctypes.c_void_p
 EncoderLayerFwdArgs = _struct('EncoderLayerFwdArgs', 'sst_encoder_layer_fwd_args of include/sst_amd.h', (
     [('m', c_i64), ('n_windows', c_i64)] + [(k, ctypes.c_int32) for k in ('n_heads', 'act', 'max_tokens', 'impl')]
@@ -410,6 +421,14 @@ _SIGNATURES = {
     'sst_roi_loss_fwd_f32': (c_i32, [c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_roi_loss_bwd_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_roi_decode_f32': (c_i32, [c_ptr, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_anchor_targets_gt_chunk': (c_i32, []),
+    'sst_anchor_block': (c_i32, []),
+    'sst_anchor_targets_f32': (c_i32, [c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                       c_ptr]),
+    'sst_anchor_loss_workspace_bytes': (c_i64, [c_i32, c_i32, c_i32]),
+    'sst_anchor_loss_fwd_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_anchor_loss_bwd_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_anchor_decode_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
