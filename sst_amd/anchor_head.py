@@ -22,6 +22,7 @@ from torch import nn
 from . import _lib
 from . import box_ops
 from . import roi_head  # noqa: F401  (registers DeltaXYZWLHRBBoxCoder)
+from ._head_common import cfg_get as _get
 from .center_head import build_bbox_coder
 from .detectors import HEADS, NECKS
 from .norm import build_conv_layer, build_norm_layer
@@ -33,14 +34,6 @@ MAX_SIZES, MAX_ROTS = 8, 4                         # SST_ANCHOR_MAX_SIZES, SST_A
 
 def build_anchor_generator(cfg):
     return ANCHOR_GENERATORS.build(cfg)
-
-
-def _get(cfg, key, default=None):
-    if cfg is None:
-        return default
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
 
 
 def limit_period(val, offset=0.5, period=np.pi):

@@ -11,10 +11,12 @@ The head's network (shared convolution, SeparateHead / DCNSeparateHead), SECONDF
 their configs in ``self.unbuilt`` and ``forward`` raises.  fp32 device tensors only; CPU tensors raise.
 """
 import ctypes
+import functools
 
 import torch
 from torch import nn
 
+from . import _head_common
 from . import _lib
 from . import box_ops
 from .detectors import HEADS
@@ -29,11 +31,7 @@ def build_bbox_coder(cfg):
     return BBOX_CODERS.build(cfg)
 
 
-def _check_f32(*tensors):
-    _lib.require_cuda(*tensors)
-    for t in tensors:
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError(f'sst_amd.center_head: float32 tensors expected, got {t.dtype}')
+_check_f32 = functools.partial(_head_common.check_f32, 'sst_amd.center_head')
 
 
 def center_targets_box_tile():

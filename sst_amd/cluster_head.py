@@ -11,32 +11,24 @@ fp32 device tensors only; CPU, non-fp32 or non-contiguous inputs raise.
 """
 import copy
 import ctypes
+import functools
 
 import torch
 from torch import nn
 
+from . import _head_common
 from . import _lib
 from . import box_ops
+from ._head_common import LOSS_COUNTS, LOSS_FINISH, cfg_get as _cfg_get, dist_world as _dist_world
 from .center_head import BBOX_CODERS, build_bbox_coder
 from .detectors import HEADS, build_head
 from .sst_ops import build_mlp
 
 STATUS_BAD_LABEL, STATUS_BAD_FLAG = 1, 2
-LOSS_COUNTS, LOSS_FINISH = 1, 2
 LOSS_NAMES = ('loss_cls', 'loss_center', 'loss_size', 'loss_rot', 'loss_vel')
 
-
-def _check_f32(*tensors):
-    _lib.require_cuda(*tensors)
-    for t in tensors:
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError(f'sst_amd.cluster_head: float32 tensors expected, got {t.dtype}')
-
-
-def _check(t, dtype, shape, what):
-    _lib.require_cuda(t)
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f'sst_amd.cluster_head: {what} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
+_check_f32 = functools.partial(_head_common.check_f32, 'sst_amd.cluster_head')
+_check = functools.partial(_head_common.check, 'sst_amd.cluster_head')
 
 
 def cluster_max_tasks():
@@ -160,13 +152,6 @@ def _task_array(logits, regs, labels, tgts, wts, d_logits=None, d_regs=None):
         arr[t].d_reg_preds = d_regs[t].data_ptr() if d_regs is not None else None
         arr[t].classes = logits[t].size(1)
     return arr
-
-
-def _dist_world():
-    dist = torch.distributed
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_world_size()
-    return 1
 
 
 class _ClusterLoss(torch.autograd.Function):
@@ -354,12 +339,6 @@ class FSDSeparateHead(nn.Module):
 
     def forward(self, x):
         return {attr_name: self.__getattr__(attr_name)(x) for attr_name in self.attrs}
-
-
-def _cfg_get(cfg, key, default=None):
-    if cfg is None:
-        return default
-    return cfg.get(key, default) if hasattr(cfg, 'get') else getattr(cfg, key, default)
 
 
 def _check_l1(name, cfg):

@@ -25,6 +25,7 @@
 // through fp64 (correct rounding whatever the build flags).  log / sin / cos are the device library's; the decoder's exp and
 // sigmoid are evaluated in fp64 and rounded once.
 #include "common.h"
+#include "head_math.h"
 
 #pragma clang fp contract(off)
 
@@ -36,9 +37,6 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kChunk = 128;               // ground-truth boxes per LDS pass
 constexpr int kMaxSizes = SST_ANCHOR_MAX_SIZES, kMaxRots = SST_ANCHOR_MAX_ROTS;
 constexpr int kFinalThreads = 1024;
-constexpr float kPi = 3.14159265358979323846f;       // (float)np.pi
-constexpr float kTwoPi = 6.28318530717958647692f;    // (float)(2 * np.pi)
-constexpr float kQuarterPi = 0.78539816339744830962f;  // (float)(np.pi / 4)
 
 struct Grid {
   const float* xs;  // [n_sizes, W]
@@ -209,11 +207,12 @@ struct LossArgs {
 // One logit z against the 0 / 1 target of mmdet's py_sigmoid_focal_loss:
 //   pt = sigmoid(z) (target 0) or 1 - sigmoid(z) (target 1) = sigmoid(u), u = z or -z
 //   e = (alpha or 1 - alpha) pt^gamma softplus(u);  de/du = (...) pt^gamma (gamma (1 - pt) softplus(u) + pt)
+// Not sst_focal_elem: this one forms (aw * pt^gamma) * softplus where that forms (bce * aw) * mod, and calls powf for every gamma
+// other than 2, so the last bit can differ.
 __device__ __forceinline__ void focal_term(float z, bool target, float alpha, float gamma, float& loss, float& dz) {
   const float u = target ? -z : z;
-  const float e = expf(-fabsf(u));
-  const float hi = 1.f / (1.f + e), lo = e * hi;
-  const float pt = u >= 0.f ? hi : lo, qt = u >= 0.f ? lo : hi;
+  float pt, qt;
+  const float e = sst_sigmoid_pair(u, pt, qt);
   const float sp = fmaxf(u, 0.f) + log1pf(e);
   const float ptg = gamma == 2.f ? pt * pt : powf(pt, gamma);
   const float aw = target ? alpha : 1.f - alpha;
@@ -222,12 +221,10 @@ __device__ __forceinline__ void focal_term(float z, bool target, float alpha, fl
   dz = target ? -du : du;
 }
 
-__device__ __forceinline__ float sqrt_rn(float v) { return (float)sqrt((double)v); }
-
 // DeltaXYZWLHRBBoxCoder.encode(anchor, gt) and get_direction_target
 __device__ __forceinline__ int encode_box(const float* an, const float* gt, float dir_offset, float* tg) {
   const float za = an[2] + an[5] / 2.f, zg = gt[2] + gt[5] / 2.f;
-  const float diagonal = sqrt_rn(an[4] * an[4] + an[3] * an[3]);
+  const float diagonal = sst_sqrt_rn(an[4] * an[4] + an[3] * an[3]);
   tg[0] = (gt[0] - an[0]) / diagonal;
   tg[1] = (gt[1] - an[1]) / diagonal;
   tg[2] = (zg - za) / an[5];
@@ -267,6 +264,7 @@ __device__ __forceinline__ void positive_terms(const LossArgs& a, const float* a
       q = cp * st;
       chain = cp * ct + sp * st;  // d(p - q) / d pred
     }
+    // sst_reg_elem / sst_reg_grad of (diff, smooth_l1 ? beta : 0), written out: through the helpers this kernel needs more VGPRs
     const float diff = p - q, ad = fabsf(diff);
     float e, de;
     if (a.smooth_l1 && ad < a.beta) {
@@ -284,30 +282,12 @@ __device__ __forceinline__ void positive_terms(const LossArgs& a, const float* a
   if (has_dir) {
     // softmax cross entropy of two logits: softplus(z_other - z_target)
     const float u = dir_t ? dir0 - dir1 : dir1 - dir0;
-    const float e = expf(-fabsf(u));
+    float p_other, p_target;
+    const float e = sst_sigmoid_pair(u, p_other, p_target);
     l_dir = fmaxf(u, 0.f) + log1pf(e);
-    const float hi = 1.f / (1.f + e), lo = e * hi;
-    const float p_other = u >= 0.f ? hi : lo;
     d_dir0 = dir_t ? p_other : -p_other;
     d_dir1 = dir_t ? -p_other : p_other;
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;  // lane 0: lanes added in a fixed tree
-}
-
-// sum over the workgroup in a fixed order (lanes by the shuffle tree, then the waves in index order); the result in thread 0
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = wsum[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += wsum[w];
-  return r;
 }
 
 // A lane per (sample, cell): its ns * nr anchors in turn.  The logits, box codes and direction logits are read where they lie
@@ -386,9 +366,9 @@ __global__ __launch_bounds__(kThreads) void anchor_loss_k(LossArgs a, double* __
     }
   }
   if (!kBackward) {
-    sum_cls = block_sum(sum_cls, wsum);
-    sum_box = block_sum(sum_box, wsum);
-    sum_dir = block_sum(sum_dir, wsum);
+    sum_cls = sst_block_sum(sum_cls, wsum);
+    sum_box = sst_block_sum(sum_box, wsum);
+    sum_dir = sst_block_sum(sum_dir, wsum);
     if (threadIdx.x == 0) {
       partials[3 * (int64_t)blockIdx.x] = sum_cls;
       partials[3 * (int64_t)blockIdx.x + 1] = sum_box;
@@ -408,9 +388,9 @@ __global__ __launch_bounds__(kFinalThreads) void anchor_loss_final_k(const doubl
     s1 += partials[3 * (int64_t)r + 1];
     s2 += partials[3 * (int64_t)r + 2];
   }
-  s0 = block_sum(s0, wsum);
-  s1 = block_sum(s1, wsum);
-  s2 = block_sum(s2, wsum);
+  s0 = sst_block_sum(s0, wsum);
+  s1 = sst_block_sum(s1, wsum);
+  s2 = sst_block_sum(s2, wsum);
   if (threadIdx.x == 0) {
     double avg = 0.0;
     for (int b = 0; b < batch; ++b) avg += (double)max(counts[b], 1);
@@ -451,7 +431,7 @@ __global__ __launch_bounds__(kThreads) void anchor_decode_k(Grid g, const float*
 #pragma unroll
   for (int c = 0; c < 7; ++c) d[c] = box[((int64_t)t * 7 + c) * hw + cell];
   const float za = an[2] + an[5] / 2.f;
-  const float diagonal = sqrt_rn(an[4] * an[4] + an[3] * an[3]);
+  const float diagonal = sst_sqrt_rn(an[4] * an[4] + an[3] * an[3]);
   const float xg = d[0] * diagonal + an[0], yg = d[1] * diagonal + an[1];
   float zg = d[2] * an[5] + za;
   const float lg = (float)exp((double)d[4]) * an[4], wg = (float)exp((double)d[3]) * an[3];

@@ -20,6 +20,7 @@
 // log / sin / cos are the device library's.  Losses: mmdet is not part of the reference tree; the formulas are those of
 // include/sst_amd.h.
 #include "common.h"
+#include "head_math.h"
 
 namespace {
 
@@ -52,23 +53,20 @@ struct TargetsArgs {
   char* out;
 };
 
-// the correctly rounded fp32 root: 53 >= 2 * 24 + 2 bits, so the fp64 root rounded to fp32 is the exact rounding
-__device__ __forceinline__ float sqrt_rn(float v) { return (float)sqrt((double)v); }
-
 // gaussian_radius((height, width), min_overlap), gaussian.py:56-85, in the reference's fp32 operation order
 __device__ __forceinline__ float gaussian_radius(float height, float width, const TargetsArgs& a) {
   const float hw = height + width;
   const float b1 = hw;
   const float c1 = width * height * a.k_1m / a.k_1p;
-  const float sq1 = sqrt_rn(b1 * b1 - 4.f * c1);
+  const float sq1 = sst_sqrt_rn(b1 * b1 - 4.f * c1);
   const float r1 = (b1 + sq1) / 2.f;
   const float b2 = 2.f * hw;
   const float c2 = a.k_1m * width * height;
-  const float sq2 = sqrt_rn(b2 * b2 - 16.f * c2);
+  const float sq2 = sst_sqrt_rn(b2 * b2 - 16.f * c2);
   const float r2 = (b2 + sq2) / 2.f;
   const float b3 = a.k_m2 * hw;
   const float c3 = a.k_m1 * width * height;
-  const float sq3 = sqrt_rn(b3 * b3 - a.k_16 * c3);
+  const float sq3 = sst_sqrt_rn(b3 * b3 - a.k_16 * c3);
   const float r3 = (b3 + sq3) / 2.f;
   float r = r1;  // Python's min(r1, r2, r3)
   if (r2 < r) r = r2;
@@ -195,9 +193,8 @@ struct BoxArgs {
 // dp/dz = p q where the clamp is inactive (0 where it is active, as torch's clamp gives):
 //   de/dz = [t == 1] q^2 (2 p log(p) - q) + (1 - t)^4 p^2 (p - 2 q log(q))
 __device__ __forceinline__ void focal_cell(float z, float t, float& loss, float& dz) {
-  const float e = expf(-fabsf(z));
-  const float hi = 1.f / (1.f + e), lo = e * hi;
-  float p = z >= 0.f ? hi : lo, q = z >= 0.f ? lo : hi;
+  float p, q;
+  sst_sigmoid_pair(z, p, q);
   const float kLo = 1e-4f;
   bool clamped = false;
   if (p < kLo) {
@@ -214,23 +211,6 @@ __device__ __forceinline__ void focal_cell(float z, float t, float& loss, float&
   const bool pos = t == 1.f;
   loss = (pos ? -lp * (q * q) : 0.f) - lq * (p * p) * nw;
   dz = clamped ? 0.f : (pos ? (q * q) * (2.f * p * lp - q) : 0.f) + nw * (p * p) * (p - 2.f * q * lq);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;  // lane 0: lanes added in a fixed tree
-}
-
-// sum over the workgroup in a fixed order (lanes by the shuffle tree, then the waves in index order); the result in thread 0
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = wsum[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += wsum[w];
-  return r;
 }
 
 // partial record of a workgroup: [0] the sum of its cells' terms (double bits), [1] its count of cells with t == 1
@@ -250,8 +230,8 @@ __global__ __launch_bounds__(kCtrThreads) void center_loss_partial_k(const float
       npos += t == 1.f ? 1.0 : 0.0;
     }
   }
-  sum = block_sum(sum, wsum);
-  npos = block_sum(npos, wsum);  // integers below 2^53: exact
+  sum = sst_block_sum(sum, wsum);
+  npos = sst_block_sum(npos, wsum);  // integers below 2^53: exact
   if (threadIdx.x == 0) {
     partials[2 * (int64_t)blockIdx.x] = (unsigned long long)__double_as_longlong(sum);
     partials[2 * (int64_t)blockIdx.x + 1] = (unsigned long long)(long long)npos;
@@ -270,8 +250,8 @@ __global__ __launch_bounds__(kBoxThreads) void center_loss_final_k(const unsigne
     sum += __longlong_as_double((long long)partials[2 * (int64_t)r]);
     npos += (double)(long long)partials[2 * (int64_t)r + 1];
   }
-  sum = block_sum(sum, wsum);
-  npos = block_sum(npos, wsum);
+  sum = sst_block_sum(sum, wsum);
+  npos = sst_block_sum(npos, wsum);
   double box = 0.0, nmask = 0.0;
   const int64_t slots = (int64_t)a.batch * a.max_objs;
   for (int64_t s = tid; s < slots; s += kBoxThreads) {
@@ -290,8 +270,8 @@ __global__ __launch_bounds__(kBoxThreads) void center_loss_final_k(const unsigne
     for (int c = 0; c < kCode; ++c)
       if (c < a.n_code) box += (double)(fabsf(pred[c] - tgt[c]) * a.cw[c]);
   }
-  box = block_sum(box, wsum);
-  nmask = block_sum(nmask, wsum);
+  box = sst_block_sum(box, wsum);
+  nmask = sst_block_sum(nmask, wsum);
   if (tid == 0) {
     out[0] = (float)(sum / fmax(npos, 1.0) * (double)w_cls);
     out[1] = (float)(box / (double)((float)nmask + 1e-4f) * (double)w_bbox);  // avg_factor = mask.float().sum() + 1e-4 is fp32

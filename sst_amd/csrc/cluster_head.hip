@@ -21,6 +21,7 @@
 // tree's own py_sigmoid_focal_loss, sum / avg_factor, L1 is sum(|pred - target| weight) / avg_factor.
 // Checked against the reference's methods run from their source text (tests/golden/cluster_head_train.npz).
 #include "common.h"
+#include "head_math.h"
 #include "pib_test.h"
 
 namespace {
@@ -193,58 +194,6 @@ struct LossArgs {
   float beta[5];       // SmoothL1Loss beta of the regression losses (same order; 0: L1Loss)
 };
 
-// rows [r0, r0 + rows) of a [n, c] matrix -> the [class][row] LDS image, by consecutive lanes reading consecutive floats
-__device__ __forceinline__ void stage_rows(const float* __restrict__ src, int64_t r0, int rows, int c, float* img) {
-  const float* base = src + r0 * c;
-  const int total = rows * c;
-  for (int i = threadIdx.x; i < total; i += kThreads) {
-    const int r = i / c, k = i - r * c;
-    img[k * kLd + r] = base[i];
-  }
-}
-
-__host__ __device__ __forceinline__ int image_floats(int c) { return (c * kLd + 3) / 4 * 4; }
-
-__device__ __forceinline__ float pow_gamma(float q, float gamma) {
-  if (gamma == 2.f) return q * q;
-  if (gamma == 3.f) return q * q * q;
-  if (gamma == 1.f) return q;
-  if (gamma == 0.f) return 1.f;
-  return powf(q, gamma);
-}
-
-// One element of the sigmoid focal loss at z with target t (the derivation is in seg_loss.hip):
-//   e = (max(z, 0) - t z + log1p(exp(-|z|))) * (t ? alpha : 1 - alpha) * q^gamma,   q = |t - p|
-//   de/dz = (t ? alpha : 1 - alpha) * s * q^gamma * (q + gamma * bce * (1 - q)),    s = 1 - 2t
-// p and 1 - p are both formed from exp(-|z|) without a subtraction, so q keeps its relative accuracy at |z| = 60.
-__device__ __forceinline__ void focal_elem(float z, bool t, float alpha, float gamma, float& loss, float& dz) {
-  const float e = expf(-fabsf(z));
-  const float a = 1.f / (1.f + e), b = e * a;
-  const float p = z >= 0.f ? a : b, pc = z >= 0.f ? b : a;
-  const float q = t ? pc : p, qc = t ? p : pc;
-  const float bce = fmaxf(z, 0.f) - (t ? z : 0.f) + log1pf(e);
-  const float aw = t ? alpha : 1.f - alpha;
-  const float mod = pow_gamma(q, gamma);
-  loss = bce * aw * mod;
-  dz = (t ? -aw : aw) * mod * (q + gamma * bce * qc);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;  // lane 0: lanes added in a fixed tree
-}
-
-// one regression element: |d| (L1Loss, beta == 0) or mmdet's smooth_l1_loss, 0.5 d^2 / beta below beta and |d| - 0.5 beta above
-__device__ __forceinline__ float reg_elem(float d, float beta) {
-  const float ad = fabsf(d);
-  return ad < beta ? 0.5f * ad * ad / beta : ad - 0.5f * beta;
-}
-// its derivative in d: d / beta below beta, sign(d) above (sign(0) = 0)
-__device__ __forceinline__ float reg_grad(float d, float beta) {
-  return fabsf(d) < beta ? d / beta : d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f;
-}
-
 // the loss a regression column belongs to: 1 center, 2 size, 3 rot, 4 vel
 __device__ __forceinline__ constexpr int group_of(int col) { return col < 3 ? 1 : col < 6 ? 2 : col < 8 ? 3 : 4; }
 
@@ -269,7 +218,7 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_partial_k(LossArgs a, i
     if (r0 >= a.n) break;
     const int rows = (int)min((int64_t)kSub, a.n - r0);
     __syncthreads();
-    stage_rows(tk.logits, r0, rows, c, img);
+    sst_stage_rows<kThreads, kLd>(tk.logits, r0, rows, c, img);
     __syncthreads();
     const bool live = tid < rows;
     const int64_t r = r0 + tid;
@@ -281,8 +230,8 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_partial_k(LossArgs a, i
     if (ok) {
       const float* col = img + tid;
       for (int k = 0; k < c; ++k) {
-        float e, dz;
-        focal_elem(col[k * kLd], lab == k, a.alpha, a.gamma, e, dz);
+        float p, e, dz;
+        sst_focal_elem(col[k * kLd], lab == k, a.alpha, a.gamma, p, e, dz);
         s0 += (double)e;
       }
     }
@@ -295,7 +244,7 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_partial_k(LossArgs a, i
       for (int k = 0; k < kMaxCode; ++k) {
         if (k < code) {
           const float w = wt[k];
-          const double v = (double)(reg_elem(pr[k] - tg[k], a.beta[group_of(k)]) * (w * a.cw[k]));
+          const double v = (double)(sst_reg_elem(pr[k] - tg[k], a.beta[group_of(k)]) * (w * a.cw[k]));
           if (group_of(k) == 1) s1 += v;
           else if (group_of(k) == 2) s2 += v;
           else if (group_of(k) == 3) s3 += v;
@@ -307,11 +256,11 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_partial_k(LossArgs a, i
     if (__any(bad_flag)) status |= 2;
   }
   // the workgroup's record: lanes by a fixed shuffle tree, then the four waves in order
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  s3 = wave_sum(s3);
-  s4 = wave_sum(s4);
+  s0 = sst_wave_sum(s0);
+  s1 = sst_wave_sum(s1);
+  s2 = sst_wave_sum(s2);
+  s3 = sst_wave_sum(s3);
+  s4 = sst_wave_sum(s4);
   if (lane == 0) {
     wsum[0][wave] = s0;
     wsum[1][wave] = s1;
@@ -323,11 +272,8 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_partial_k(LossArgs a, i
   }
   __syncthreads();
   unsigned long long* rec = partials + ((int64_t)blockIdx.y * nb + blockIdx.x) * kRecord;
-  if (tid < 5) {
-    double v = wsum[tid][0];
-    for (int w = 1; w < kWaves; ++w) v += wsum[tid][w];
-    rec[tid] = (unsigned long long)__double_as_longlong(v);
-  } else if (tid < kRecord) {
+  sst_write_record<kWaves, 5>(wsum, rec);
+  if (tid >= 5 && tid < kRecord) {
     const int j = tid - 5;
     long long v = 0;
     for (int w = 0; w < kWaves; ++w) v = j == 1 ? (v | wcnt[j][w]) : (v + wcnt[j][w]);
@@ -396,7 +342,7 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_bwd_k(LossArgs a, const
   const sst_cluster_loss_task& tk = a.task[blockIdx.y];
   const int c = tk.classes, code = a.code;
   float* img = (float*)smem;             // [c][kLd]
-  float* regbuf = img + image_floats(c);  // [kSub][code]
+  float* regbuf = img + sst_image_floats<kLd>(c);  // [kSub][code]
   const int64_t r0 = (int64_t)blockIdx.x * kSub;
   const int rows = (int)min((int64_t)kSub, a.n - r0);
   const double* cnt = counts + blockIdx.y * 4;
@@ -408,7 +354,7 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_bwd_k(LossArgs a, const
 #pragma unroll
   for (int j = 1; j < 4; ++j) kk[j] = any ? (float)((double)gt[j] * (double)a.w[j] / reg_avg) : 0.f;
   kk[4] = any ? (float)((double)gt[4] * (double)a.w[4] / (2.0 * n_pos)) : 0.f;
-  stage_rows(tk.logits, r0, rows, c, img);
+  sst_stage_rows<kThreads, kLd>(tk.logits, r0, rows, c, img);
   __syncthreads();
   if (tid < rows) {
     const int64_t r = r0 + tid;
@@ -417,8 +363,8 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_bwd_k(LossArgs a, const
     const bool ok = pos || lab == c;
     float* col = img + tid;
     for (int k = 0; k < c; ++k) {
-      float e, dz = 0.f;
-      if (ok) focal_elem(col[k * kLd], lab == k, a.alpha, a.gamma, e, dz);
+      float p, e, dz = 0.f;
+      if (ok) sst_focal_elem(col[k * kLd], lab == k, a.alpha, a.gamma, p, e, dz);
       col[k * kLd] = ok ? kk[0] * dz : 0.f;
     }
     const float* pr = tk.reg_preds + r * code;
@@ -429,7 +375,7 @@ __global__ __launch_bounds__(kThreads) void cluster_loss_bwd_k(LossArgs a, const
       if (k < code) {
         float v = 0.f;
         if (pos) {
-          v = reg_grad(pr[k] - tg[k], a.beta[group_of(k)]) * ((wt[k] * a.cw[k]) * kk[group_of(k)]);
+          v = sst_reg_grad(pr[k] - tg[k], a.beta[group_of(k)]) * ((wt[k] * a.cw[k]) * kk[group_of(k)]);
         }
         regbuf[tid * code + k] = v;
       }
@@ -640,7 +586,7 @@ extern "C" int sst_cluster_loss_fwd_f32(const sst_cluster_loss_task* tasks, int 
   const int nb = (int)sst_div_up(n, kTileRows);
   hipStream_t s = (hipStream_t)stream;
   if (phases & SST_CLUSTER_LOSS_COUNTS) {
-    const size_t lds = kImageAt + (size_t)image_floats(max_classes(a)) * sizeof(float);
+    const size_t lds = kImageAt + (size_t)sst_image_floats<kLd>(max_classes(a)) * sizeof(float);
     hipLaunchKernelGGL(cluster_loss_partial_k, dim3(nb, n_tasks), dim3(kThreads), lds, s, a, nb,
                        (unsigned long long*)d_workspace);
     SST_LAUNCH_CHECK();
@@ -665,7 +611,7 @@ extern "C" int sst_cluster_loss_bwd_f32(const sst_cluster_loss_task* tasks, int 
   const int rc = fill_loss_args(a, tasks, n_tasks, n, code_size, gamma, alpha, code_weight, loss_weights, smooth_l1_beta, true);
   if (rc != SST_OK) return rc;
   if (!d_g || !d_counts) return SST_ERR_ARG;
-  const size_t lds = (size_t)(image_floats(max_classes(a)) + kSub * code_size) * sizeof(float);
+  const size_t lds = (size_t)(sst_image_floats<kLd>(max_classes(a)) + kSub * code_size) * sizeof(float);
   hipLaunchKernelGGL(cluster_loss_bwd_k, dim3((unsigned)sst_div_up(n, kSub), n_tasks), dim3(kThreads), lds, (hipStream_t)stream,
                      a, d_g, d_counts);
   SST_LAUNCH_CHECK();

@@ -20,6 +20,7 @@
 // reference's fp32 operation order; sin / cos / log / exp are the device library's.
 #include "common.h"
 #include "bev_clip.h"
+#include "head_math.h"
 
 namespace {
 
@@ -30,9 +31,6 @@ constexpr int kMaxCls = SST_ROI_MAX_CLASSES;
 constexpr int kMaxPieces = SST_ROI_MAX_PIECES;
 constexpr int kMaxProps = 8192;      // proposals of one sample the sampler holds in LDS (keys 32 KB + 2 x 8 KB of flags)
 constexpr int kRec = 5;              // 8-byte slots of a loss record: cls, reg, corner sums (double), num_pos, corner rows (int64)
-constexpr float kTwoPi = 6.283185307179586f;
-constexpr float kPi = 3.141592653589793f;
-constexpr float kHalfPi = 1.5707963267948966f;
 
 // ------------------------------------------------------------------------------------------------------------------
 // assignment: IoU of every proposal with the boxes of its sample (and class)
@@ -395,20 +393,6 @@ __global__ __launch_bounds__(kThreads) void roi_sample_k(sst_roi_sample_args a) 
 // losses
 // ------------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;  // lane 0: lanes added in a fixed tree
-}
-
-__device__ __forceinline__ float reg_elem(float d, float beta) {
-  const float ad = fabsf(d);
-  return ad < beta ? 0.5f * ad * ad / beta : ad - 0.5f * beta;
-}
-__device__ __forceinline__ float reg_grad(float d, float beta) {
-  return fabsf(d) < beta ? d / beta : d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f;
-}
-
 // corner k of LiDARInstance3DBoxes.corners in units of (w, l, h): unravel_index(k, [2, 2, 2])[[0, 1, 3, 2, 4, 5, 7, 6]] - (.5, .5, 0)
 __device__ __forceinline__ void corner_norm(int k, float& nx, float& ny, float& nz) {
   const int y = (k >> 1) & 1;
@@ -508,14 +492,14 @@ __global__ __launch_bounds__(kThreads) void roi_loss_partial_k(sst_roi_loss_args
       const float* bp = a.bbox_pred + r * 7;
       const float* tg = a.targets + r * 7;
 #pragma unroll
-      for (int k = 0; k < 7; ++k) s1 += (double)(reg_elem(bp[k] - tg[k], a.beta) * a.code_weight[k]);
+      for (int k = 0; k < 7; ++k) s1 += (double)(sst_reg_elem(bp[k] - tg[k], a.beta) * a.code_weight[k]);
       if (f.corner) s2 = (double)corner_row(bp, a.rois + r * a.roi_cols + 1, a.gts + (int64_t)a.gt_index[r] * a.gt_cols, nullptr);
     }
   }
   const long long n_reg = __popcll(__ballot(reg)), n_corner = __popcll(__ballot(corner));
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
+  s0 = sst_wave_sum(s0);
+  s1 = sst_wave_sum(s1);
+  s2 = sst_wave_sum(s2);
   if (lane == 0) {
     wsum[0][wave] = s0;
     wsum[1][wave] = s1;
@@ -525,11 +509,8 @@ __global__ __launch_bounds__(kThreads) void roi_loss_partial_k(sst_roi_loss_args
   }
   __syncthreads();
   unsigned long long* rec = partials + (int64_t)blockIdx.x * kRec;
-  if (tid < 3) {
-    double v = wsum[tid][0];
-    for (int w = 1; w < kWaves; ++w) v += wsum[tid][w];
-    rec[tid] = (unsigned long long)__double_as_longlong(v);
-  } else if (tid < kRec) {
+  sst_write_record<kWaves, 3>(wsum, rec);
+  if (tid >= 3 && tid < kRec) {
     long long v = 0;
     for (int w = 0; w < kWaves; ++w) v += wcnt[tid - 3][w];
     rec[tid] = (unsigned long long)v;
@@ -596,7 +577,7 @@ __global__ __launch_bounds__(kThreads) void roi_loss_bwd_k(sst_roi_loss_args a, 
     const float* bp = a.bbox_pred + r * 7;
     const float* tg = a.targets + r * 7;
 #pragma unroll
-    for (int k = 0; k < 7; ++k) db[k] = reg_grad(bp[k] - tg[k], a.beta) * (a.code_weight[k] * k_reg);
+    for (int k = 0; k < 7; ++k) db[k] = sst_reg_grad(bp[k] - tg[k], a.beta) * (a.code_weight[k] * k_reg);
     if (f.corner) {
       float gc[7];
       corner_row(bp, a.rois + r * a.roi_cols + 1, a.gts + (int64_t)a.gt_index[r] * a.gt_cols, gc);

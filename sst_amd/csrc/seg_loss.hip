@@ -19,6 +19,7 @@
 // by N (not by the sum of the class weights) in cross-entropy mode is mmseg's documented behaviour and is unpinned beyond that.
 // Checked against the reference's methods run from their source text (tests/golden/seg_head_train.npz).
 #include "common.h"
+#include "head_math.h"
 #include "pib_test.h"
 
 namespace {
@@ -112,9 +113,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_targets_k(
     }
     const float d[3] = {__fsub_rn(cx, x), __fsub_rn(cy, y), __fsub_rn(cz, z)};
 #pragma unroll
-    // The root must be the correctly rounded one.  __fsqrt_rn is the approximate v_sqrt_f32 in a default build; the fp64
-    // root of an fp32 number, rounded to fp32, is exact rounding (53 >= 2 * 24 + 2 bits) whatever the build flags are.
-    for (int k = 0; k < 3; ++k) t[k] = d[k] == 0.f ? 0.f : copysignf((float)sqrt((double)fabsf(d[k])), d[k]);
+    for (int k = 0; k < 3; ++k) t[k] = d[k] == 0.f ? 0.f : copysignf(sst_sqrt_rn(fabsf(d[k])), d[k]);  // the correctly rounded root
   }
   vote_targets[p * 3] = t[0];
   vote_targets[p * 3 + 1] = t[1];
@@ -143,54 +142,11 @@ struct LossArgs {
 // [2] num_valid, [3] status, [4] num_fg, [5, 5 + C) tp, [5 + C, 5 + 2C) real (int64)
 __host__ __device__ __forceinline__ int record_slots(int c) { return 5 + 2 * c; }
 
-// rows [r0, r0 + rows) of a [n, c] matrix -> the [class][row] LDS image, by consecutive lanes reading consecutive floats
-__device__ __forceinline__ void stage_rows(const float* __restrict__ src, int64_t r0, int rows, int c, float* img) {
-  const float* base = src + r0 * c;
-  const int total = rows * c;
-  for (int i = threadIdx.x; i < total; i += kSegThreads) {
-    const int r = i / c, k = i - r * c;
-    img[k * kLossLd + r] = base[i];
-  }
-}
-
 // dynamic LDS of the two row kernels, every offset a multiple of 16 bytes: the wave sums (forward only), then the image
 constexpr int kWaveCounters = 3 + 2 * kMaxClasses;
 constexpr int kWaveCountersAt = 2 * (kSegThreads / 64) * 8;
 constexpr int kImageAt = kWaveCountersAt + (kSegThreads / 64) * kWaveCounters * 8;
 static_assert(kWaveCountersAt % 16 == 0 && kImageAt % 16 == 0, "LDS carve offsets");
-__host__ __device__ __forceinline__ int image_floats(int c) { return (c * kLossLd + 3) / 4 * 4; }
-
-__device__ __forceinline__ float pow_gamma(float q, float gamma) {
-  if (gamma == 2.f) return q * q;
-  if (gamma == 3.f) return q * q * q;
-  if (gamma == 1.f) return q;
-  if (gamma == 0.f) return 1.f;
-  return powf(q, gamma);
-}
-
-// One element of the sigmoid focal loss at z with target t: the probability p, the loss term and its derivative in z.
-//   e = (max(z, 0) - t z + log1p(exp(-|z|))) * (t ? alpha : 1 - alpha) * q^gamma,   q = |t - p|
-// sigmoid(|z|) = 1 / (1 + exp(-|z|)) and its complement exp(-|z|) / (1 + exp(-|z|)) are formed without a subtraction, so
-// q keeps its relative accuracy at |z| = 60.  With s = 1 - 2t: p - t = s q and dq/dz = s q (1 - q), hence
-//   de/dz = (t ? alpha : 1 - alpha) * s * q^gamma * (q + gamma * bce * (1 - q)).
-__device__ __forceinline__ void focal_elem(float z, bool t, float alpha, float gamma, float& p, float& loss, float& dz) {
-  const float e = expf(-fabsf(z));
-  const float a = 1.f / (1.f + e), b = e * a;
-  p = z >= 0.f ? a : b;
-  const float pc = z >= 0.f ? b : a;
-  const float q = t ? pc : p, qc = t ? p : pc;
-  const float bce = fmaxf(z, 0.f) - (t ? z : 0.f) + log1pf(e);
-  const float aw = t ? alpha : 1.f - alpha;
-  const float mod = pow_gamma(q, gamma);
-  loss = bce * aw * mod;
-  dz = (t ? -aw : aw) * mod * (q + gamma * bce * qc);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;  // lane 0: lanes added in a fixed tree
-}
 
 __global__ __launch_bounds__(kSegThreads) void seg_loss_partial_k(LossArgs a, unsigned long long* __restrict__ partials) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -198,8 +154,8 @@ __global__ __launch_bounds__(kSegThreads) void seg_loss_partial_k(LossArgs a, un
   const int c = a.c;
   double(*wsum)[kSegThreads / 64] = (double(*)[kSegThreads / 64])smem;
   long long(*wcnt)[kWaveCounters] = (long long(*)[kWaveCounters])(smem + kWaveCountersAt);
-  float* img = (float*)(smem + kImageAt);  // [c][kLossLd]
-  float* gsc = img + image_floats(c);      // [n_groups][kSegThreads]: the group scores of this thread's row
+  float* img = (float*)(smem + kImageAt);           // [c][kLossLd]
+  float* gsc = img + sst_image_floats<kLossLd>(c);  // [n_groups][kSegThreads]: the group scores of this thread's row
   const bool sigmoid = a.mode == SST_SEG_SIGMOID_FOCAL;
   const bool stats = a.score_thresh != nullptr;
   const int64_t tile0 = (int64_t)blockIdx.x * kLossTileRows;
@@ -211,7 +167,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_loss_partial_k(LossArgs a, un
     if (r0 >= a.n) break;
     const int rows = (int)min((int64_t)kLossSub, a.n - r0);
     __syncthreads();
-    stage_rows(a.logits, r0, rows, c, img);
+    sst_stage_rows<kSegThreads, kLossLd>(a.logits, r0, rows, c, img);
     __syncthreads();
     const bool live = tid < rows;
     const int64_t r = r0 + tid;
@@ -238,7 +194,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_loss_partial_k(LossArgs a, un
         bool hit = false;
         if (ok) {
           float p, e, dz;
-          focal_elem(a.scale * col[k * kLossLd], t, a.alpha, a.gamma, p, e, dz);
+          sst_focal_elem(a.scale * col[k * kLossLd], t, a.alpha, a.gamma, p, e, dz);
           sem += (double)e;
           hit = stats && t && p > a.score_thresh[k];
         }
@@ -285,8 +241,8 @@ __global__ __launch_bounds__(kSegThreads) void seg_loss_partial_k(LossArgs a, un
     }
   }
   // the workgroup's record: lanes by a fixed shuffle tree, then the four waves in order
-  sem = wave_sum(sem);
-  vote = wave_sum(vote);
+  sem = sst_wave_sum(sem);
+  vote = sst_wave_sum(vote);
   if (lane == 0) {
     wsum[0][wave] = sem;
     wsum[1][wave] = vote;
@@ -300,11 +256,8 @@ __global__ __launch_bounds__(kSegThreads) void seg_loss_partial_k(LossArgs a, un
   }
   __syncthreads();
   unsigned long long* rec = partials + (int64_t)blockIdx.x * record_slots(c);
-  if (tid < 2) {
-    double v = wsum[tid][0];
-    for (int w = 1; w < kSegThreads / 64; ++w) v += wsum[tid][w];
-    rec[tid] = (unsigned long long)__double_as_longlong(v);
-  } else if (tid < record_slots(c)) {
+  sst_write_record<kSegThreads / 64, 2>(wsum, rec);
+  if (tid >= 2 && tid < record_slots(c)) {
     const int j = tid - 2;
     long long v = 0;
     for (int w = 0; w < kSegThreads / 64; ++w) v = j == 1 ? (v | wcnt[w][j]) : (v + wcnt[w][j]);
@@ -363,8 +316,8 @@ __global__ __launch_bounds__(kSegThreads) void seg_loss_bwd_k(LossArgs a, const 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int c = a.c;
-  float* img = (float*)smem;                         // [c][kLossLd]
-  int* vote_class = (int*)(img + image_floats(c));   // the class whose three vote columns carry a gradient, or -1
+  float* img = (float*)smem;                                     // [c][kLossLd]
+  int* vote_class = (int*)(img + sst_image_floats<kLossLd>(c));  // the class whose three vote columns carry a gradient, or -1
   const bool sigmoid = a.mode == SST_SEG_SIGMOID_FOCAL;
   const int64_t r0 = (int64_t)blockIdx.x * kLossSub;
   const int rows = (int)min((int64_t)kLossSub, a.n - r0);
@@ -372,7 +325,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_loss_bwd_k(LossArgs a, const 
   const double denom = sigmoid ? (double)a.n * (double)c : (double)a.n;
   const float k_sem = (float)((double)g[0] * (double)a.scale / denom);
   const float k_vote = n_valid > 0 ? (float)((double)g[1] / (3.0 * (double)n_valid)) : 0.f;
-  stage_rows(a.logits, r0, rows, c, img);
+  sst_stage_rows<kSegThreads, kLossLd>(a.logits, r0, rows, c, img);
   const bool live = tid < rows;
   const int64_t r = r0 + tid;
   const int64_t lab = live ? a.labels[r] : -1;
@@ -387,7 +340,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_loss_bwd_k(LossArgs a, const 
     } else if (sigmoid) {
       for (int k = 0; k < c; ++k) {
         float p, e, dz;
-        focal_elem(a.scale * col[k * kLossLd], lab == k, a.alpha, a.gamma, p, e, dz);
+        sst_focal_elem(a.scale * col[k * kLossLd], lab == k, a.alpha, a.gamma, p, e, dz);
         col[k * kLossLd] = k_sem * dz;
       }
     } else {
@@ -503,7 +456,7 @@ extern "C" int sst_seg_loss_fwd_f32(const float* d_logits, const float* d_vote_p
   if (!d_out || !d_counts || !d_workspace) return SST_ERR_ARG;
   const int nb = (int)sst_div_up(n, kLossTileRows);
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = kImageAt + (size_t)(image_floats(c) + a.n_groups * kSegThreads) * sizeof(float);
+  const size_t lds = kImageAt + (size_t)(sst_image_floats<kLossLd>(c) + a.n_groups * kSegThreads) * sizeof(float);
   if (lds > 65536) return SST_ERR_UNSUPPORTED;  // 32 classes in more than 28 groups
   hipLaunchKernelGGL(seg_loss_partial_k, dim3(nb), dim3(kSegThreads), lds, s, a, (unsigned long long*)d_workspace);
   SST_LAUNCH_CHECK();
@@ -523,7 +476,7 @@ extern "C" int sst_seg_loss_bwd_f32(const float* d_logits, const float* d_vote_p
                            alpha, d_class_weight, nullptr, nullptr, 0);
   if (rc != SST_OK) return rc;
   if (!d_g || !d_counts || !d_dlogits || !d_dvote_preds) return SST_ERR_ARG;
-  const size_t lds = (size_t)(image_floats(c) + kLossSub) * sizeof(float);
+  const size_t lds = (size_t)(sst_image_floats<kLossLd>(c) + kLossSub) * sizeof(float);
   hipLaunchKernelGGL(seg_loss_bwd_k, dim3((unsigned)sst_div_up(n, kLossSub)), dim3(kSegThreads), lds, (hipStream_t)stream,
                      a, d_g, d_counts, d_dlogits, d_dvote_preds);
   SST_LAUNCH_CHECK();

@@ -26,6 +26,7 @@ from torch import nn
 
 from . import kernels as K
 from . import seg_loss
+from ._head_common import cfg_get as _get
 from .cluster import ClusterAssigner, HybridAssigner, SSGAssigner
 from .registry import BACKBONES, MODELS, ROI_EXTRACTORS, Registry, build_backbone, build_middle_encoder, build_voxel_encoder
 from .sst_ops import build_mlp, scatter_v2
@@ -56,13 +57,6 @@ def build_neck(cfg):
 
 def build_head(cfg):
     return HEADS.build(cfg)
-
-
-def _get(cfg, key, default=None):
-    """mmcv's ConfigDict answers both cfg['a'] and cfg.a; plain dicts (what the tests exec from the config text) only the first"""
-    if cfg is None:
-        return default
-    return cfg.get(key, default) if hasattr(cfg, 'get') else getattr(cfg, key, default)
 
 
 @NECKS.register_module()

@@ -10,6 +10,8 @@ from torch import distributed as dist
 from torch import nn as nn
 from torch.autograd.function import Function
 
+from ._head_common import dist_world as _dist_world
+
 
 class AllReduce(Function):
 
@@ -42,12 +44,6 @@ def _sync_bn_forward(self, input, reduce_dims):
     scale = self.weight * invstd
     bias = self.bias - mean * scale
     return scale, bias
-
-
-def _dist_world():
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_world_size()
-    return 1
 
 
 class _BatchNormActFn(Function):

@@ -10,39 +10,25 @@ sampler, then per sample the canonical transform and the encode), ``roi_loss`` (
 fp32 device tensors only; CPU, non-fp32 or non-contiguous inputs raise.
 """
 import ctypes
+import functools
 
 import torch
 from torch import nn
 from torch.nn import functional as F
 
+from . import _head_common
 from . import _lib
 from . import box_ops
+from ._head_common import LOSS_COUNTS, LOSS_FINISH, cfg_get as _cfg_get, offsets as _offsets
 from .center_head import BBOX_CODERS, build_bbox_coder
 from .detectors import HEADS, build_head
 from .registry import ROI_EXTRACTORS, build_voxel_encoder
 from .sst_ops import build_mlp
 
-LOSS_COUNTS, LOSS_FINISH = 1, 2
 MAX_CLASSES, MAX_PIECES = 16, 8
 
-
-def _check_f32(*tensors):
-    _lib.require_cuda(*tensors)
-    for t in tensors:
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError(f'sst_amd.roi_head: float32 tensors expected, got {t.dtype}')
-
-
-def _check(t, dtype, shape, what):
-    _lib.require_cuda(t)
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f'sst_amd.roi_head: {what} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}')
-
-
-def _cfg_get(cfg, key, default=None):
-    if cfg is None:
-        return default
-    return cfg.get(key, default) if hasattr(cfg, 'get') else getattr(cfg, key, default)
+_check_f32 = functools.partial(_head_common.check_f32, 'sst_amd.roi_head')
+_check = functools.partial(_head_common.check, 'sst_amd.roi_head')
 
 
 def roi_assign_gt_tile():
@@ -121,14 +107,7 @@ def roi_assign_sample(proposals, proposal_labels, gt_bboxes, gt_labels, *, num_c
     prop = torch.cat(props, 0).contiguous()
     plab = torch.cat([l.reshape(-1).to(device=dev, dtype=torch.long) for l in plabels]).contiguous()
     prop_lens, gt_lens = [p.size(0) for p in props], [g.size(0) for g in gts]
-
-    def offsets(lens):
-        off = [0]
-        for n in lens:
-            off.append(off[-1] + n)
-        return torch.tensor(off, dtype=torch.int32).to(dev, non_blocking=True)
-
-    prop_off, gt_off = offsets(prop_lens), offsets(gt_lens)
+    prop_off, gt_off = _offsets(prop_lens, dev)[0], _offsets(gt_lens, dev)[0]
     n_props, n_gts, ld = prop.size(0), gt.size(0), max(gt_lens)
     if not 1 <= num_classes <= MAX_CLASSES:
         raise RuntimeError(f'roi_assign_sample: 1 to {MAX_CLASSES} classes, got {num_classes}')

@@ -7,26 +7,19 @@ loop over the samples with a points-in-boxes launch and several boolean-index co
 ``valid_label.max()``, ``.min()`` and ``num_valid > 0`` back; here those asserts are the ``status`` word of ``counts``).
 fp32 device tensors only; CPU, non-contiguous or non-fp32 inputs raise.
 """
+import functools
+
 import torch
 
+from . import _head_common
 from . import _lib
+from ._head_common import offsets as _offsets
 
 SIGMOID_FOCAL, SOFTMAX_CE = 0, 1
 STATUS_BAD_LABEL, STATUS_MASKED_NO_CLASS = 1, 2
 
-
-def _check_f32(*tensors):
-    _lib.require_cuda(*tensors)
-    for t in tensors:
-        if t.dtype != torch.float32:
-            raise RuntimeError(f'sst_amd.seg_loss: float32 tensors expected, got {t.dtype}')
-
-
-def _check(t, dtype, shape, what):
-    _lib.require_cuda(t)
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f'sst_amd.seg_loss: {what} must be {dtype} of shape {tuple(shape)}, got {t.dtype} '
-                           f'{tuple(t.shape)}')
+_check_f32 = functools.partial(_head_common.check_f32, 'sst_amd.seg_loss')
+_check = functools.partial(_head_common.check, 'sst_amd.seg_loss')
 
 
 def seg_targets_box_tile():
@@ -37,13 +30,6 @@ def seg_targets_box_tile():
 def seg_loss_tile_rows():
     """points per workgroup of the loss forward's first launch"""
     return int(_lib.load().sst_seg_loss_tile_rows())
-
-
-def _offsets(sizes, device):
-    off = [0]
-    for s in sizes:
-        off.append(off[-1] + int(s))
-    return torch.tensor(off, dtype=torch.int32).to(device, non_blocking=True), off[-1]
 
 
 def _targets_launch(points, pt_off, batch, boxes, box_labels, box_off, extra_width, bg_label, centers):

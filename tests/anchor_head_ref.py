@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F_
 
 import box_ops_ref as B
+from head_ref_common import ulp_distance  # noqa: F401  (the tests reach it through this module)
 
 F = np.float32
 PI = np.pi
@@ -369,11 +370,3 @@ def get_bboxes_single(grid, cls_score, bbox_pred, dir_pred, cfg):
     dir_rot = limit_period(out[:, 6] - F(cfg['dir_offset']), cfg['dir_limit_offset'], PI)
     out[:, 6] = dir_rot + F(cfg['dir_offset']) + F(PI) * res['dir'].astype(F)
     return out, res['scores'], res['labels']
-
-
-def ulp_distance(a, b):
-    """element-wise distance in float32 units in the last place (monotone integer mapping of the bit patterns)"""
-    def key(v):
-        i = np.ascontiguousarray(v, F).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7fffffff), i)
-    return np.abs(key(a) - key(b))

@@ -5,6 +5,8 @@ for the tests' reference, gradients left to autograd), the decoding in float32. 
 import numpy as np
 import torch
 
+from head_ref_common import ulp_distance  # noqa: F401  (the tests reach it through this module)
+
 F = np.float32
 HEAD_CHANNELS = (2, 1, 3, 2, 2)    # reg, height, dim, rot, vel
 
@@ -213,11 +215,3 @@ def decode(heat, reg, hei, dim, rot, vel, coder, norm_bbox):
     r = np.asarray(coder['post_center_range'], F)
     keep &= (boxes[..., :3] >= r[:3]).all(2) & (boxes[..., :3] <= r[3:]).all(2)
     return boxes, scores, labels, keep
-
-
-def ulp_distance(a, b):
-    """element-wise distance in float32 units in the last place (monotone integer mapping of the bit patterns)"""
-    def key(v):
-        i = np.ascontiguousarray(v, F).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7fffffff), i)
-    return np.abs(key(a) - key(b))

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _bench_common import median_ms  # noqa: E402
 import sst_amd  # noqa: E402
 from sst_amd.anchor_head import limit_period  # noqa: E402
 
@@ -46,22 +47,6 @@ HEAD = dict(type='Anchor3DHead', num_classes=3, in_channels=384, feat_channels=3
             test_cfg=dict(use_rotate_nms=True, nms_across_levels=False, nms_pre=4096, nms_thr=0.25, score_thr=0.1, min_bbox_size=0,
                           max_num=500))
 C, N_A = 3, 6
-
-
-def median_ms(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        times.append(start.elapsed_time(stop))
-    times.sort()
-    return 0.5 * (times[(len(times) - 1) // 2] + times[len(times) // 2]), times[0]
 
 
 def host(x):

@@ -13,6 +13,7 @@ torch.profiler in a separate, untimed step; null when the profiler is not availa
 composed code: every bool() / int() / .item() of a device value and every nonzero; the fused path has none).
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -21,6 +22,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _bench_common  # noqa: E402
+from _bench_common import median_ms  # noqa: E402
 import sst_amd  # noqa: E402
 
 DEV = 'cuda:0'
@@ -31,21 +34,8 @@ CFG = dict(grid_size=[468, 468, 1], voxel_size=(0.32, 0.32, 6), out_size_factor=
            code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.0, 0.0])
 W_CLS, W_BBOX = 1.0, 2.0
 
-
-def median_ms(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        times.append(start.elapsed_time(stop))
-    times.sort()
-    return 0.5 * (times[(len(times) - 1) // 2] + times[len(times) // 2]), times[0]
+# kernels of csrc/center_head.hip against torch's glue (concatenating the lists of boxes and labels, adding the two losses)
+count_launches = functools.partial(_bench_common.count_launches, ours='center_')
 
 
 def host(x):
@@ -139,30 +129,6 @@ def scene(n_boxes, seed):
         boxes.append(b.to(DEV))
         labels.append(kind.to(DEV))
     return boxes, labels
-
-
-def count_launches(fn, names_too=False):
-    """-> dict(ours, torch, memsets): device-side kernels of csrc/center_head.hip, other kernels (torch's glue: concatenating
-    the lists of boxes and labels, adding the two losses) and memsets of one call; None without the profiler"""
-    try:
-        from torch.autograd import DeviceType
-        from torch.profiler import ProfilerActivity, profile
-        fn()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]   # not the runtime calls on the host side
-        if not names:
-            return None
-        kernels = [n for n in names if 'memcpy' not in n.lower() and 'memset' not in n.lower()]
-        ours = [n for n in kernels if 'center_' in n]
-        out = dict(ours=len(ours), torch=len(kernels) - len(ours), memsets=len([n for n in names if 'memset' in n.lower()]))
-        if names_too:
-            out['names'] = [n.replace('(anonymous namespace)::', '')[:64] for n in names]
-        return out
-    except Exception:
-        return None
 
 
 def main():

@@ -15,6 +15,7 @@ kernel launches (counted by torch.profiler in a separate, untimed step; null whe
 fused path has none).
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -22,28 +23,14 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _bench_common  # noqa: E402
+from _bench_common import median_ms  # noqa: E402
 import sst_amd  # noqa: E402
 
 DEV = 'cuda:0'
 SYNCS = [0]
 GAMMA, ALPHA = 2.0, 0.25
 WEIGHTS = [2.0, 0.5, 0.5, 0.2, 0.2]
-
-
-def median_ms(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        times.append(start.elapsed_time(stop))
-    times.sort()
-    return 0.5 * (times[(len(times) - 1) // 2] + times[len(times) // 2]), times[0]
 
 
 def masked(t, mask):
@@ -174,30 +161,8 @@ def learn_readback_names():
         pass
 
 
-def count_launches(fn, names_too=False):
-    """-> dict(ours, torch, memsets, copies) of one call: device-side kernels of csrc/cluster_head.hip, other kernels (torch's
-    glue), memsets, copies, and those copies that look like a host read; None without the profiler"""
-    try:
-        from torch.autograd import DeviceType
-        from torch.profiler import ProfilerActivity, profile
-        fn()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
-        if not names:
-            return None
-        kernels = [n for n in names if 'memcpy' not in n.lower() and 'memset' not in n.lower()]
-        ours = [n for n in kernels if 'cluster_' in n]
-        out = dict(ours=len(ours), torch=len(kernels) - len(ours), memsets=len([n for n in names if 'memset' in n.lower()]),
-                   copies=len([n for n in names if 'memcpy' in n.lower()]),
-                   device_to_host=len([n for n in names if n in READBACK_NAMES or 'dtoh' in n.lower()]))
-        if names_too:
-            out['names'] = [n.replace('(anonymous namespace)::', '')[:64] for n in names]
-        return out
-    except Exception:
-        return None
+# kernels of csrc/cluster_head.hip, and those copies that look like a host read
+count_launches = functools.partial(_bench_common.count_launches, ours='cluster_', readback_names=READBACK_NAMES)
 
 
 WAYMO = (['Car', 'Pedestrian', 'Cyclist'], [dict(class_names=['Car']), dict(class_names=['Pedestrian']),

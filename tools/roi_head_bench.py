@@ -15,6 +15,7 @@ untimed step; null when the profiler is not available) and host reads (counted i
 .item() of a device value, every boolean-mask index, nonzero and unique; the fused path has the one read of ``counts``).
 """
 import argparse
+import functools
 import json
 import math
 import os
@@ -23,6 +24,8 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _bench_common  # noqa: E402
+from _bench_common import median_ms  # noqa: E402
 import sst_amd  # noqa: E402
 from sst_amd import box_ops  # noqa: E402
 
@@ -34,21 +37,7 @@ CFG = dict(num_classes=3, class_mask=True, pos_iou_thr=[0.45, 0.35, 0.35], neg_i
 WEIGHTS = (1.0, 2.0, 1.0)
 TWO_PI = 2 * math.pi
 
-
-def median_ms(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        times.append(start.elapsed_time(stop))
-    times.sort()
-    return 0.5 * (times[(len(times) - 1) // 2] + times[len(times) // 2]), times[0]
+count_launches = functools.partial(_bench_common.count_launches, ours='roi_')  # kernels of csrc/roi_head.hip
 
 
 def read(n=1):
@@ -292,31 +281,6 @@ def scene(n_props, n_boxes, seed):
     bbox_pred = (torch.randn(rows, 7, generator=g) * 0.3).to(DEV).requires_grad_(True)
     nonempty = (torch.rand(rows, generator=g) < 0.85).to(DEV)
     return props, plabels, gts, glabels, cls_score, bbox_pred, nonempty
-
-
-def count_launches(fn, names_too=False):
-    """-> dict(ours, torch, memsets, copies) of one call: kernels of csrc/roi_head.hip, other kernels (torch's glue), memsets,
-    copies; None without the profiler"""
-    try:
-        from torch.autograd import DeviceType
-        from torch.profiler import ProfilerActivity, profile
-        fn()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
-        if not names:
-            return None
-        kernels = [n for n in names if 'memcpy' not in n.lower() and 'memset' not in n.lower()]
-        ours = [n for n in kernels if 'roi_' in n]
-        out = dict(ours=len(ours), torch=len(kernels) - len(ours), memsets=len([n for n in names if 'memset' in n.lower()]),
-                   copies=len([n for n in names if 'memcpy' in n.lower()]))
-        if names_too:
-            out['names'] = [n.replace('(anonymous namespace)::', '')[:64] for n in names]
-        return out
-    except Exception:
-        return None
 
 
 def main():

@@ -21,27 +21,12 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _bench_common import count_launches, median_ms  # noqa: E402
 import sst_amd  # noqa: E402
 from sst_amd import seg_loss  # noqa: E402
 
 DEV = 'cuda:0'
 SYNCS = [0]
-
-
-def median_ms(fn, iters, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        fn()
-        stop.record()
-        stop.synchronize()
-        times.append(start.elapsed_time(stop))
-    times.sort()
-    return 0.5 * (times[(len(times) - 1) // 2] + times[len(times) // 2]), times[0]
 
 
 def read(x):
@@ -141,17 +126,8 @@ def scene(n, n_boxes, seed):
 
 
 def count_kernels(fn):
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        fn()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        names = [e.name for e in prof.events() if 'memcpy' not in e.name.lower() and 'memset' not in e.name.lower()]
-        return len(names) if names else None
-    except Exception:
-        return None
+    n = count_launches(fn, ours='seg_')
+    return n['ours'] + n['torch'] if n else None
 
 
 def main():
@@ -210,8 +186,8 @@ def main():
                    loss_vote=abs(float(a[1]) - float(b['loss_vote'])) / abs(float(b['loss_vote'])))
         fused_ms, composed_ms = [], []
         for _ in range(3):                       # alternate the two paths: other work shares the machine
-            fused_ms.append(median_ms(fused, args.iters))
-            composed_ms.append(median_ms(composed, args.iters))
+            fused_ms.append(median_ms(fused, args.iters, warmup=5))
+            composed_ms.append(median_ms(composed, args.iters, warmup=5))
         SYNCS[0] = 0
         composed()
         syncs = SYNCS[0]
