@@ -448,6 +448,9 @@ int sst_cast_add_pos_bf16(const void* d_x, int x_is_bf16, int64_t m, int c, cons
 int sst_tall_linear_bf16(const void* d_x, int64_t ldx, const void* d_w, const float* d_bias, int64_t m, int k, int n,
                          int epilogue, const void* d_aux_in, void* d_aux_out, int64_t ldaux, void* d_y, int64_t ldy,
                          void* stream);
+/* The row partition of a sst_tall_linear_bf16 / sst_tall_linear_ln_bf16 (epi_is_ln) launch for m rows: workgroups (4 waves each,
+ * 8 under SST_AMD_BF16_LINEAR_WAVES=8) and rows per wave (a multiple of 16).  Host arithmetic only. */
+int sst_tall_linear_bf16_partition(int64_t m, int k, int n, int epi_is_ln, int64_t* blocks, int64_t* rows_per_wave);
 /* sst_tall_linear_ln_bf16: y = LayerNorm(x w^T + bias + res) - `norm(src + src2)` (sst_basic_block_v2.py:113-118) in the
  * epilogue of the projection that produces src2 (out_proj, linear2): n = 128, k = 128 or 256.  Also written: d_sum (bf16
  * [m, 128], row stride ldres like d_res; the backward pass's input; may be NULL), d_stats [m, 2] fp32 (mean, rstd), and, when

@@ -191,33 +191,46 @@ EPI_BIAS, EPI_GELU, EPI_RELU, EPI_MUL_GELU_GRAD, EPI_MUL_RELU_GRAD, EPI_ADD = ra
 _LINEAR_SHAPES = ((128, 128), (128, 256), (256, 128))
 
 
-def tall_linear(x, w, bias=None, epilogue=EPI_BIAS, aux_in=None, want_pre=False):
+def tall_linear(x, w, bias=None, epilogue=EPI_BIAS, aux_in=None, want_pre=False, out=None, pre_out=None):
     """y (bf16 [M, N]) = epilogue(x (bf16 [M, K]) @ w (bf16 [N, K])^T + bias (fp32)); csrc/dense_bf16.hip.
-    epilogue GELU / RELU with want_pre: -> (y, pre-activation bf16); MUL_*_GRAD / ADD read ``aux_in`` (bf16 [M, N])."""
+    epilogue GELU / RELU with want_pre: -> (y, pre-activation bf16); MUL_*_GRAD / ADD read ``aux_in`` (bf16 [M, N]).
+    ``out`` / ``pre_out``: optional preallocated bf16 [M, N] tensors (any row stride) for y / the pre-activation."""
     m, k = x.shape
     n = w.size(0)
     if (k, n) not in _LINEAR_SHAPES or w.size(1) != k or x.dtype != BF16 or w.dtype != BF16 or not w.is_contiguous():
         raise RuntimeError(f'sst_amd.bf16.tall_linear: unsupported operands {tuple(x.shape)} x {tuple(w.shape)}')
-    y = torch.empty((m, n), dtype=BF16, device=x.device)
-    pre = torch.empty((m, n), dtype=BF16, device=x.device) if want_pre else None
+    for t in (out, pre_out):
+        if t is not None and (t.shape != (m, n) or t.dtype != BF16 or t.device != x.device):
+            raise RuntimeError('sst_amd.bf16.tall_linear: out / pre_out must be bf16 [M, N] tensors on the operands\' device')
+    y = out if out is not None else torch.empty((m, n), dtype=BF16, device=x.device)
+    pre = (pre_out if pre_out is not None else torch.empty((m, n), dtype=BF16, device=x.device)) if want_pre else None
     aux = aux_in if aux_in is not None else pre
     rc = _lib.load().sst_tall_linear_bf16(_lib.ptr(x), _ld(x), _lib.ptr(w), _lib.ptr(bias), m, k, n, int(epilogue),
                                           _lib.ptr(aux_in), _lib.ptr(pre), _ld(aux) if aux is not None else 0,
-                                          _lib.ptr(y), n, _lib.stream_ptr())
+                                          _lib.ptr(y), _ld(y), _lib.stream_ptr())
     _lib.check(rc, 'sst_tall_linear_bf16')
     return (y, pre) if want_pre else y
 
 
-def linear_add_ln(x, w, bias, res, ln_weight, ln_bias, eps, save_sum=True, pos=None):
+def linear_add_ln(x, w, bias, res, ln_weight, ln_bias, eps, save_sum=True, pos=None, out=None):
     """(y, s, stats, y_plus_pos) with y = LayerNorm(x @ w^T + bias + res): the projection and `norm(src + src2)` in one
-    kernel (csrc/dense_bf16.hip, kEpiAddLN); w bf16 [128, K], K = 128 | 256."""
+    kernel (csrc/dense_bf16.hip, kEpiAddLN); w bf16 [128, K], K = 128 | 256.
+    ``out``: optional dict of preallocated contiguous tensors by the names y, s, stats, yp."""
     m, k = x.shape
     if w.shape != (128, k) or k not in (128, 256) or x.dtype != BF16 or res.shape != (m, 128) or not res.is_contiguous():
         raise RuntimeError('sst_amd.bf16.linear_add_ln: unsupported operands')
-    y = torch.empty((m, 128), dtype=BF16, device=x.device)
-    s = torch.empty((m, 128), dtype=BF16, device=x.device) if save_sum else None
-    stats = torch.empty((m, 2), dtype=torch.float32, device=x.device)
-    yp = torch.empty((m, 128), dtype=BF16, device=x.device) if pos is not None else None
+    out = out or {}
+    for name, t in out.items():
+        want = ((m, 2), torch.float32) if name == 'stats' else ((m, 128), BF16)
+        if name not in ('y', 's', 'stats', 'yp') or t.shape != want[0] or t.dtype != want[1] or not t.is_contiguous():
+            raise RuntimeError('sst_amd.bf16.linear_add_ln: out holds contiguous y | s | yp (bf16 [M, 128]) and stats (fp32 [M, 2])')
+
+    def e(name, cols, dtype=BF16):
+        return out[name] if name in out else torch.empty((m, cols), dtype=dtype, device=x.device)
+    y = e('y', 128)
+    s = e('s', 128) if save_sum else None
+    stats = e('stats', 2, torch.float32)
+    yp = e('yp', 128) if pos is not None else None
     rc = _lib.load().sst_tall_linear_ln_bf16(
         _lib.ptr(x), _ld(x), _lib.ptr(w), _lib.ptr(bias), m, k, _lib.ptr(res), 128, _lib.ptr(ln_weight), _lib.ptr(ln_bias),
         float(eps), _lib.ptr(y), _lib.ptr(s), _lib.ptr(stats), _lib.ptr(pos[0]) if pos is not None else None,
@@ -383,18 +396,20 @@ def tail_fwd(o, x, packed, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, save=Tru
     return out
 
 
-def tail_bwd(dy2, dy2p, s2, st2, pre, s1, st1, packed, n1w, n2w, act):
-    """-> (ds2, dpre, ds1, d_o (bf16), dn fp32 [4, 128] = dn2w | dn2b | dn1w | dn1b)"""
+def tail_bwd(dy2, dy2p, s2, st2, pre, s1, st1, packed, n1w, n2w, act, out=None):
+    """-> (ds2, dpre, ds1, d_o (bf16), dn fp32 [4, 128] = dn2w | dn2b | dn1w | dn1b); ``out``: optional dict of preallocated
+    contiguous tensors by the names ds2, dpre, ds1, d_o, dn and ws (the workspace, uint8)"""
     import ctypes
     m = dy2.size(0)
     dev = dy2.device
+    out = out or {}
 
-    def e(cols):
-        return torch.empty((m, cols), dtype=BF16, device=dev)
-    ds2, dpre, ds1, d_o = e(128), e(256), e(128), e(128)
-    dn = torch.empty((4, 128), dtype=torch.float32, device=dev)
+    def e(name, cols):
+        return out[name] if name in out else torch.empty((m, cols), dtype=BF16, device=dev)
+    ds2, dpre, ds1, d_o = e('ds2', 128), e('dpre', 256), e('ds1', 128), e('d_o', 128)
+    dn = out['dn'] if 'dn' in out else torch.empty((4, 128), dtype=torch.float32, device=dev)
     lib = _lib.load()
-    ws = _lib.workspace(lib.sst_encoder_tail_bwd_bf16_workspace_bytes(m), dev)
+    ws = out['ws'] if 'ws' in out else _lib.workspace(lib.sst_encoder_tail_bwd_bf16_workspace_bytes(m), dev)
     P = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     d0 = dn.data_ptr()
     args = _lib.EncoderTailBwdBF16Args(m, 1 if act == 'gelu' else 2, 0, P(dy2), P(dy2p), P(s2), P(st2), P(pre), P(s1), P(st1),

@@ -291,27 +291,40 @@ __global__ __launch_bounds__(NTH, (NTH == 512 ? 2 : (K * N <= 128 * 128 ? 3 : 2)
   }
 }
 
-template <int K, int N, int EPI>
-int launch_linear(const bf16_t* x, int64_t ldx, const bf16_t* w, const float* bias, int64_t m, bf16_t* y, int64_t ldy,
-                  const bf16_t* aux_in, bf16_t* aux_out, int64_t ldaux, hipStream_t st, const ln_epi ln = ln_epi()) {
-  constexpr int lds = N * K * 2 + N * 4 * (EPI == kEpiAddLN ? 3 : 1);
-  // SST_AMD_BF16_LINEAR_WAVES = 8: one 8-wave workgroup per CU (the weights are copied to LDS once per CU, not 2-3 times)
+// SST_AMD_BF16_LINEAR_WAVES = 8: one 8-wave workgroup per CU (the weights are copied to LDS once per CU, not 2-3 times);
+// read once per process
+int linear_threads() {
   static int nth = 0;
   if (nth == 0) {
     const char* e = getenv("SST_AMD_BF16_LINEAR_WAVES");
     nth = (e != nullptr && atoi(e) == 8) ? 512 : 256;
   }
+  return nth;
+}
+
+// persistent shape: every wave a contiguous row range (multiple of 16 rows)
+void linear_partition(int64_t m, int lds, int nth, int64_t& blocks, int64_t& rpw) {
+  const int wpb = nth / 64;
+  blocks = nth == 512 ? 256 : 256 * (lds <= 40 * 1024 ? 3 : 2);
+  rpw = sst_align_up(sst_div_up(m, blocks * wpb), 16);
+  blocks = sst_div_up(m, rpw * wpb);
+}
+
+constexpr int linear_lds_bytes(int k, int n, bool is_ln) { return n * k * 2 + n * 4 * (is_ln ? 3 : 1); }
+
+template <int K, int N, int EPI>
+int launch_linear(const bf16_t* x, int64_t ldx, const bf16_t* w, const float* bias, int64_t m, bf16_t* y, int64_t ldy,
+                  const bf16_t* aux_in, bf16_t* aux_out, int64_t ldaux, hipStream_t st, const ln_epi ln = ln_epi()) {
+  constexpr int lds = linear_lds_bytes(K, N, EPI == kEpiAddLN);
+  const int nth = linear_threads();
   static unsigned long long configured = 0;     // the attribute belongs to a (kernel, device) pair
   if (sst_first_use_on_device(&configured)) {
     SST_HIP(hipFuncSetAttribute((const void*)tall_linear_bf16_k<K, N, EPI, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     SST_HIP(hipFuncSetAttribute((const void*)tall_linear_bf16_k<K, N, EPI, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     sst_mark_device(&configured);
   }
-  // persistent shape: every wave a contiguous row range (multiple of 16 rows)
-  const int wpb = nth / 64;
-  int64_t blocks = nth == 512 ? 256 : 256 * (lds <= 40 * 1024 ? 3 : 2);
-  int64_t rpw = sst_align_up(sst_div_up(m, blocks * wpb), 16);
-  blocks = sst_div_up(m, rpw * wpb);
+  int64_t blocks, rpw;
+  linear_partition(m, lds, nth, blocks, rpw);
   if (nth == 512)
     hipLaunchKernelGGL((tall_linear_bf16_k<K, N, EPI, 512>), dim3((unsigned)blocks), dim3(512), lds, st, x, ldx, w, bias, m,
                        (int)rpw, y, ldy, aux_in, aux_out, ldaux, ln);
@@ -668,6 +681,15 @@ int sst_tall_linear_bf16(const void* d_x, int64_t ldx, const void* d_w, const fl
   return SST_OK;
 }
 
+
+/* How a launch of tall_linear_bf16_k cuts m rows: workgroups (4 waves, or 8 under SST_AMD_BF16_LINEAR_WAVES=8) and the rows a
+ * wave walks.  Host arithmetic only (no launch): the tests take their boundary token counts from it. */
+int sst_tall_linear_bf16_partition(int64_t m, int k, int n, int epi_is_ln, int64_t* blocks, int64_t* rows_per_wave) {
+  if (m <= 0 || !blocks || !rows_per_wave) return SST_ERR_ARG;
+  if (!((k == 128 && n == 128) || (k == 128 && n == 256 && !epi_is_ln) || (k == 256 && n == 128))) return SST_ERR_UNSUPPORTED;
+  linear_partition(m, linear_lds_bytes(k, n, epi_is_ln != 0), linear_threads(), *blocks, *rows_per_wave);
+  return SST_OK;
+}
 
 int sst_tall_linear_ln_bf16(const void* d_x, int64_t ldx, const void* d_w, const float* d_bias, int64_t m, int k,
                             const void* d_res, int64_t ldres, const float* d_ln_weight, const float* d_ln_bias, float eps,

@@ -192,11 +192,13 @@ __device__ __forceinline__ void mma_tiles(const unsigned char* img, int lane_off
 }
 
 __device__ __forceinline__ void ln_stats(f32x4 (&v)[4][2], float eps, float& mean, float& rstd) {
-  float sum = 0.f;
+  float sum = 0.f;   // the lane's 32 values in the order the LayerNorm epilogue of csrc/dense_bf16.hip adds them: the same statistics
 #pragma unroll
   for (int s = 0; s < 4; ++s)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sum += v[s][0][r] + v[s][1][r];
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sum += v[s][h][r];
   sum += __shfl_xor(sum, 16, 64);
   sum += __shfl_xor(sum, 32, 64);
   mean = sum * (1.f / 128.f);
@@ -305,13 +307,17 @@ __global__ __launch_bounds__(kNTH, 4) void encoder_tail_fwd_bf16_k(const tail_fw
     for (int tp = 0; tp < 2; ++tp) {
       const int nl = kHC * j + 32 * tp + 8 * g;
       const f32x4 p0 = a1[2 * tp] + *(const f32x4*)(par + 6 * kC + nl), p1 = a1[2 * tp + 1] + *(const f32x4*)(par + 6 * kC + nl + 4);
-      f32x4 h0, h1;
+      // the activation acts on the ROUNDED pre-activation (the stored one), as the epilogue of csrc/dense_bf16.hip does: the
+      // backward pass takes the derivative at the stored value
+      const u32x4 pb = pack8(p0, p1);
+      f32x4 q0, q1, h0, h1;
+      unpack8(pb, q0, q1);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        h0[r] = ACT == 1 ? gelu_f(p0[r]) : fmaxf(p0[r], 0.f);
-        h1[r] = ACT == 1 ? gelu_f(p1[r]) : fmaxf(p1[r], 0.f);
+        h0[r] = ACT == 1 ? gelu_f(q0[r]) : fmaxf(q0[r], 0.f);
+        h1[r] = ACT == 1 ? gelu_f(q1[r]) : fmaxf(q1[r], 0.f);
       }
-      store32<true>(io, P.pre, kFF, kHC * j + 32 * tp, pack8(p0, p1));
+      store32<true>(io, P.pre, kFF, kHC * j + 32 * tp, pb);
       hb[tp] = pack8(h0, h1);
       store32<true>(io, P.h, kFF, kHC * j + 32 * tp, hb[tp]);
     }

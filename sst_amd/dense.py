@@ -495,18 +495,20 @@ def encoder_tail_fwd(o, x, packed, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, 
     return out
 
 
-def encoder_tail_bwd(dy2, dy2p, s2, st2, pre, s1, st1, packed, n1w, n2w, act):
+def encoder_tail_bwd(dy2, dy2p, s2, st2, pre, s1, st1, packed, n1w, n2w, act, out=None):
     """the backward of encoder_tail_fwd up to the attention output: -> (ds2, dpre, ds1, d_o, dn [4, 128] = dn2w | dn2b | dn1w | dn1b);
-    the weight gradients of the three linears are left to the caller (ds2 with h, dpre with y1, ds1 with o)."""
+    the weight gradients of the three linears are left to the caller (ds2 with h, dpre with y1, ds1 with o).
+    ``out``: optional dict of preallocated contiguous tensors by the names ds2, dpre, ds1, d_o, dn and ws (the workspace, uint8)."""
     m = dy2.size(0)
     dev = dy2.device
+    out = out or {}
 
-    def e(cols):
-        return torch.empty((m, cols), dtype=torch.float32, device=dev)
-    ds2, dpre, ds1, d_o = e(128), e(256), e(128), e(128)
-    dn = torch.empty((4, 128), dtype=torch.float32, device=dev)
+    def e(name, cols):
+        return out[name] if name in out else torch.empty((m, cols), dtype=torch.float32, device=dev)
+    ds2, dpre, ds1, d_o = e('ds2', 128), e('dpre', 256), e('ds1', 128), e('d_o', 128)
+    dn = out['dn'] if 'dn' in out else torch.empty((4, 128), dtype=torch.float32, device=dev)
     lib = _lib.load()
-    ws = _lib.workspace(lib.sst_encoder_tail_bwd_workspace_bytes(m), dev)
+    ws = out['ws'] if 'ws' in out else _lib.workspace(lib.sst_encoder_tail_bwd_workspace_bytes(m), dev)
     P = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     d0 = dn.data_ptr()
     args = _lib.EncoderTailBwdArgs(m, 1 if act == 'gelu' else 2, 0, P(dy2), P(dy2p), P(s2), P(st2), P(pre), P(s1), P(st1), P(packed),

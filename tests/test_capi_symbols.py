@@ -119,3 +119,20 @@ def test_header_is_plain_c_and_cpp(tmp_path):
         pytest.skip('no gcc')
     subprocess.run(['gcc', '-std=c99', '-Wall', '-Werror', '-fsyntax-only', '-I', inc, str(src)], check=True)
     subprocess.run(['g++', '-std=c++17', '-Wall', '-Werror', '-fsyntax-only', '-I', inc, '-x', 'c++', str(src)], check=True)
+
+
+def test_bf16_linear_partition_is_host_arithmetic():
+    """sst_tall_linear_bf16_partition (the arithmetic launch_linear of csrc/dense_bf16.hip uses) answers without a GPU: the rows
+    are covered, a wave's range is a multiple of 16 rows, and the shapes the kernels are not built for are refused"""
+    from sst_amd import _lib
+    lib = _lib.load()
+    b, r = ctypes.c_int64(), ctypes.c_int64()
+    wpw = 8 if os.environ.get('SST_AMD_BF16_LINEAR_WAVES') == '8' else 4
+    for k, n, ln in ((128, 128, 0), (128, 256, 0), (256, 128, 0), (128, 128, 1), (256, 128, 1)):
+        for m in (1, 49, 50, 4099, 90107, 1 << 20):
+            assert lib.sst_tall_linear_bf16_partition(m, k, n, ln, ctypes.byref(b), ctypes.byref(r)) == 0
+            assert r.value % 16 == 0 and r.value >= 16 and b.value * wpw * r.value >= m > (b.value - 1) * wpw * r.value
+    assert lib.sst_tall_linear_bf16_partition(0, 128, 128, 0, ctypes.byref(b), ctypes.byref(r)) == _lib.SST_ERR_ARG
+    assert lib.sst_tall_linear_bf16_partition(5, 128, 128, 0, None, ctypes.byref(r)) == _lib.SST_ERR_ARG
+    assert lib.sst_tall_linear_bf16_partition(5, 64, 128, 0, ctypes.byref(b), ctypes.byref(r)) == _lib.SST_ERR_UNSUPPORTED
+    assert lib.sst_tall_linear_bf16_partition(5, 128, 256, 1, ctypes.byref(b), ctypes.byref(r)) == _lib.SST_ERR_UNSUPPORTED
