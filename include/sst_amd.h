@@ -1746,6 +1746,83 @@ int sst_anchor_decode_f32(const sst_anchor_grid* grid, const float* d_cls_score,
                           const float* d_dir_pred, const int64_t* d_inds, int64_t n, int num_classes, float* d_boxes,
                           float* d_scores, int64_t* d_dir, float* d_bev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FSD foreground sampling (csrc/fg_sample.hip): the stage between the segmentor and the clustering.
+ *
+ * sst_fg_sample_f32 - replaces SingleStageFSD.sample, get_fg_mask and get_sample_beg_position
+ * (mmdet3d/models/detectors/single_stage_fsd.py:698-797) for all classes and all samples of a batch: three launches and one
+ * memset, no host read.  mask[c][i] = sigmoid_f32(logits[i][c]) > thresholds[c], ORed with extra_mask[c][i] (bool [C, n] or
+ * NULL; logits may be NULL, then extra_mask alone decides).  batch_idx (int32, or int64 when batch_is_i64) must be
+ * non-decreasing with values in [0, batch); a value outside is counted nowhere and sets bit 0 of the status word.  With
+ * apply_rule, class c gets the first point of EVERY present sample whenever some sample up to the largest one present has no
+ * selected point of class c (:725-727; the decision is taken on the device).
+ *   Outputs: slot int32 [C, n] (the row within the class, or -1), mask bool [C, n], and in concatenated layout (class after
+ *   class, class c from row class_off[c]) src int32 (the point of every row), centers [.., 3] = points[:, :3] + votes[:, 3c:3c+3]
+ *   (one fp32 add), batch_out (the type of batch_idx), points_out [.., point_cols]; the last three may be NULL.  Each holds up
+ *   to C * n rows; a row at or beyond max_rows is not written.  With sample_major the rows are ordered by sample and, inside a
+ *   sample, class after class (inside a class in point order): slot then holds that output row, and aux int32 [C, n] (or
+ *   NULL) rides along: aux_out[row] = aux[c][i], aux_inv[aux[c][i]] = row where aux is in [0, aux_rows).  info int32 [sst_fg_sample_info_words(C)] = totals[C] | rule[C] | class_off[C + 1] | status: what the host
+ *   reads, once.  num_classes <= SST_FG_MAX_CLASSES, else SST_ERR_UNSUPPORTED.
+ *
+ * sst_fg_slot2_i32 - update_sample_results_by_mask (:571-586) for the masks: d_keep int64 [keep_offsets[C]] are the rows of
+ * every class that pass the cluster filter, ascending within a class, class after class (keep_offsets: C + 1 HOST values);
+ * d_slot2 int32 [C, n] = the row in the combined output or -1, d_final_mask bool [C, n] = slot2 >= 0.
+ *
+ * sst_fg_gather_cat_fwd_f32 - the per-class indexing of seg_logits / seg_vote_preds / seg_feats / seg_points (:738-744), the
+ * second indexing by the valid mask (:584), combine_classes (:588-593) and the column concatenation (:532) as one gather
+ * through idx int32 [m] into the n source rows: out [m, c_logits + c_votes + c_feats], points_out [m, c_points]; an index
+ * outside [0, n) gives zeros.
+ * sst_fg_roi_cat_fwd_f32 - the rows of FSD.prepare_multi_class_roi_input / prepare_roi_input
+ * (mmdet3d/models/detectors/two_stage_fsd.py:108-178): d_out [rows, cluster_cols + feat_cols] = (cluster_feats[d_row[g]], zeros
+ * where d_row[g] is outside [0, n_cluster) | seg_feats[d_src[g]], zeros where d_src[g] is outside [0, n_points)), d_src == NULL:
+ * the identity.
+ * sst_fg_gather_cat_bwd_f32 - d_feats_grad[i][f] = sum over the classes in ascending order of
+ * d_out_grad[slot2[c][i]][col0 + f] (d_out_grad has `rows` rows; a slot outside them adds nothing), zeros where no class holds the point: every element written, no float atomic.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_FG_MAX_CLASSES 32
+typedef struct sst_fg_sample_args {
+  const float* logits;
+  const float* votes;
+  const float* points;
+  const void* batch_idx;
+  const uint8_t* extra_mask;
+  int32_t* slot;
+  uint8_t* mask;
+  int32_t* src;
+  float* centers;
+  void* batch_out;
+  float* points_out;
+  int32_t* info;
+  const int32_t* aux;
+  int32_t* aux_out;
+  int32_t* aux_inv;
+  int64_t n, ld_logits, ld_votes, ld_points, max_rows, aux_rows;
+  int32_t num_classes, point_cols, batch, batch_is_i64, apply_rule, sample_major;
+  float thresholds[SST_FG_MAX_CLASSES];
+} sst_fg_sample_args;
+typedef struct sst_fg_gather_args {
+  const int32_t* idx;
+  const float* logits;
+  const float* votes;
+  const float* feats;
+  const float* points;
+  float* out;
+  float* points_out;
+  int64_t m, n, ld_logits, ld_votes, ld_feats, ld_points;
+  int32_t c_logits, c_votes, c_feats, c_points;
+} sst_fg_gather_args;
+int64_t sst_fg_sample_workspace_bytes(int64_t n, int num_classes, int batch);
+int sst_fg_sample_info_words(int num_classes);
+int sst_fg_sample_f32(const sst_fg_sample_args* args, void* d_workspace, void* stream);
+int sst_fg_slot2_i32(const int32_t* d_slot, int64_t n, int num_classes, const int64_t* d_keep, const int64_t* keep_offsets,
+                     int32_t* d_slot2, uint8_t* d_final_mask, void* stream);
+int sst_fg_gather_cat_fwd_f32(const sst_fg_gather_args* args, void* stream);
+int sst_fg_roi_cat_fwd_f32(const int32_t* d_src, const int32_t* d_row, int64_t rows, int64_t n_points, int64_t n_cluster,
+                           const float* d_cluster_feats, int64_t ld_cluster, int cluster_cols, const float* d_seg_feats,
+                           int64_t ld_feats, int feat_cols, float* d_out, void* stream);
+int sst_fg_gather_cat_bwd_f32(const float* d_out_grad, int64_t rows, int64_t ld_out, int col0, const int32_t* d_slot2, int64_t n,
+                              int num_classes, int feat_cols, float* d_feats_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,8 @@ from .roi_head import (DeltaXYZWLHRBBoxCoder, FullySparseBboxHead, GroupCorrecti
 from . import anchor_head  # noqa: F401
 from .anchor_head import (ANCHOR_GENERATORS, SECONDFPN, AlignedAnchor3DRangeGenerator, Anchor3DHead, Anchor3DRangeGenerator,  # noqa: F401
                           anchor_decode, anchor_loss, anchor_targets, build_anchor_generator)
+from . import fg_sample  # noqa: F401
+from .fg_sample import (fg_gather_cat, fg_sample_launch, roi_input, roi_input_single)  # noqa: F401
 
 __version__ = '0.1.0'
 
@@ -86,4 +88,5 @@ __all__ = [
     'GroupCorrectionHead',
     'anchor_head', 'anchor_targets', 'anchor_loss', 'anchor_decode', 'Anchor3DHead', 'SECONDFPN', 'ANCHOR_GENERATORS',
     'Anchor3DRangeGenerator', 'AlignedAnchor3DRangeGenerator', 'build_anchor_generator',
+    'fg_sample', 'fg_sample_launch', 'fg_gather_cat', 'roi_input', 'roi_input_single',
 ]

@@ -87,6 +87,17 @@ AnchorLossArgs = _struct('AnchorLossArgs', 'sst_anchor_loss_args of include/sst_
     + [(k, ctypes.c_float) for k in ('gamma', 'alpha', 'w_cls', 'w_bbox', 'w_dir', 'beta', 'pos_weight', 'dir_offset')]
     + [('code_weight', ctypes.c_float * 7), ('reserved_f', ctypes.c_float)]))
 
+FgSampleArgs = _struct('FgSampleArgs', 'sst_fg_sample_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('logits', 'votes', 'points', 'batch_idx', 'extra_mask', 'slot', 'mask', 'src', 'centers',
+                                    'batch_out', 'points_out', 'info', 'aux', 'aux_out', 'aux_inv')]
+    + [(k, c_i64) for k in ('n', 'ld_logits', 'ld_votes', 'ld_points', 'max_rows', 'aux_rows')]
+    + [(k, _I32) for k in ('num_classes', 'point_cols', 'batch', 'batch_is_i64', 'apply_rule', 'sample_major')]
+    + [('thresholds', ctypes.c_float * 32)]))
+FgGatherArgs = _struct('FgGatherArgs', 'sst_fg_gather_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('idx', 'logits', 'votes', 'feats', 'points', 'out', 'points_out')]
+    + [(k, c_i64) for k in ('m', 'n', 'ld_logits', 'ld_votes', 'ld_feats', 'ld_points')]
+    + [(k, _I32) for k in ('c_logits', 'c_votes', 'c_feats', 'c_points')]))
+
 _P = ctypes.c_void_p
 EncoderLayerFwdArgs = _struct('EncoderLayerFwdArgs', 'sst_encoder_layer_fwd_args of include/sst_amd.h', (
     [('m', c_i64), ('n_windows', c_i64)] + [(k, ctypes.c_int32) for k in ('n_heads', 'act', 'max_tokens', 'impl')]
@@ -430,6 +441,13 @@ _SIGNATURES = {
     'sst_anchor_loss_fwd_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_anchor_loss_bwd_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_anchor_decode_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_fg_sample_workspace_bytes': (c_i64, [c_i64, c_i32, c_i32]),
+    'sst_fg_sample_info_words': (c_i32, [c_i32]),
+    'sst_fg_sample_f32': (c_i32, [c_ptr, c_ptr, c_ptr]),
+    'sst_fg_slot2_i32': (c_i32, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_fg_gather_cat_fwd_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_fg_roi_cat_fwd_f32': (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
+    'sst_fg_gather_cat_bwd_f32': (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

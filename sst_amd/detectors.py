@@ -24,12 +24,13 @@ Reference:
 import torch
 from torch import nn
 
+from . import fg_sample as FS
 from . import kernels as K
 from . import seg_loss
 from ._head_common import cfg_get as _get
 from .cluster import ClusterAssigner, HybridAssigner, SSGAssigner
 from .registry import BACKBONES, MODELS, ROI_EXTRACTORS, Registry, build_backbone, build_middle_encoder, build_voxel_encoder
-from .sst_ops import build_mlp, scatter_v2
+from .sst_ops import build_mlp, scatter_v2, unique_with_plan
 from .virtual_voxel import VirtualVoxelExtractor
 from .voxel import Voxelization
 
@@ -482,7 +483,38 @@ class _HotPathDetector(nn.Module):
         self.print_info, self.runtime_info = {}, {}
 
     def combine_classes(self, data_dict, name_list):
+        """single_stage_fsd.py:588-593.  A dictionary that ``update_sample_results_by_mask`` made over the kernels carries the
+        classes combined already (``data_dict['combined']``: one gather wrote them); any other dictionary of per-class lists is
+        concatenated as the reference does."""
+        done = data_dict.get('combined') if isinstance(data_dict, dict) else None
+        if done is not None:
+            return {name: done[name] for name in name_list if name in done}
         return {name: torch.cat(data_dict[name], 0) for name in data_dict if name in name_list}
+
+    def attach_heads(self):
+        """Opt in to the training and test steps: build the heads whose configs are parked in ``self.unbuilt`` as submodules, by
+        the calls the heads document (``build_head(dict(det.unbuilt['bbox_head'], train_cfg=det.train_cfg,
+        test_cfg=det.test_cfg))``; ``roi_head`` with the ``rcnn`` parts).  ``unbuilt`` stays as it is; a detector without this
+        call constructs exactly as before (same ``state_dict`` keys).  -> self"""
+        cfg = self.unbuilt['bbox_head']
+        if cfg.get('type') != 'SparseClusterHeadV2':
+            raise NotImplementedError(f"attach_heads: bbox_head {cfg.get('type')} - the FSD step is built over SparseClusterHeadV2 "
+                                      '(FSDV2Head / SingleStageFSDV2 / FSDV2 are out of scope)')
+        self.bbox_head = build_head(dict(cfg, train_cfg=self.train_cfg, test_cfg=self.test_cfg))
+        roi = self.unbuilt.get('roi_head')
+        if roi is not None:
+            self.roi_head = build_head(dict(roi, train_cfg=_get(self.train_cfg, 'rcnn', None), test_cfg=_get(self.test_cfg, 'rcnn', None)))
+        return self
+
+    def _require_heads(self, what):
+        if getattr(self, 'bbox_head', None) is None or ('roi_head' in self.unbuilt and getattr(self, 'roi_head', None) is None):
+            raise RuntimeError(f'{type(self).__name__}.{what}: the heads are not built - call attach_heads() first (the detector '
+                               'parks their configs in `unbuilt` until then)')
+
+
+def bbox3d2result(bboxes, scores, labels):
+    """mmdet3d.core.bbox3d2result: the results of one sample on the host"""
+    return dict(boxes_3d=bboxes.to('cpu'), scores_3d=scores.cpu(), labels_3d=labels.cpu())
 
 
 @DETECTORS.register_module()
@@ -519,6 +551,181 @@ class SingleStageFSD(_HotPathDetector):
             out['cluster_pts_feats'], out['cluster_pts_xyz'] = out_pts_feats, points
         return out
 
+    # ------------------------------------------------------------------------------------------------------------------
+    # the stage between the segmentor and the clustering (single_stage_fsd.py:571-615, 698-816) over csrc/fg_sample.hip
+    # ------------------------------------------------------------------------------------------------------------------
+    def pre_voxelize(self, data_dict):
+        """single_stage_fsd.py:595-615: one grouping (``unique_with_plan``), one segmented mean per float tensor over its plan"""
+        batch_idx, points = data_dict['batch_idx'], data_dict['seg_points']
+        vs = K.const_tensor(self.cfg['pre_voxelization_size'], points.device)
+        lo = K.const_tensor(self.cluster_assigner.point_cloud_range[:3], points.device)
+        coors = torch.div(points[:, :3] - lo[None], vs[None], rounding_mode='floor').long()[:, [2, 1, 0]]
+        coors = torch.cat([batch_idx.long()[:, None], coors], dim=1)
+        new_coors, unq_inv = unique_with_plan(coors)
+        out = {}
+        for name, data in data_dict.items():
+            if torch.is_tensor(data) and data.dtype in (torch.float, torch.float16):
+                out[name] = scatter_v2(data, coors, mode='avg', return_inv=False, new_coors=new_coors, unq_inv=unq_inv)[0]
+        out['batch_idx'] = new_coors[:, 0]
+        return out
+
+    def _fg_inputs(self, seg_logits, seg_points, batch_idx, gt_bboxes_3d, gt_labels_3d):
+        """what get_fg_mask decides per class (:756-797) as the kernel's inputs: (float32-rounded thresholds, extra mask)"""
+        cfg = self.train_cfg if self.training else self.test_cfg
+        n_cls, extra = self.num_classes, None
+        if self.training and _get(self.train_cfg, 'disable_pretrain', False) and not self.runtime_info.get('enable_detection', False):
+            topks = _get(self.train_cfg, 'disable_pretrain_topks', [100, 100, 100])
+            thr = [float('inf')] * n_cls                 # the top-k indices replace the threshold
+            extra = FS.topk_extra_mask(seg_logits, topks)
+        else:
+            buffer_thr = self.runtime_info.get('threshold_buffer', 0) if (self.training and self.runtime_info is not None) else 0
+            thr = FS.round_thresholds(list(self.cfg['score_thresh'])[:n_cls], buffer_thr)
+        if _get(cfg, 'add_gt_fg_points', False):
+            extra = FS.gt_extra_mask(seg_points, batch_idx, gt_bboxes_3d, gt_labels_3d, n_cls, out=extra)
+        return thr, extra
+
+    def _num_samples(self, batch_idx, batch_size=None):
+        if batch_size is None:
+            batch_size = getattr(self, '_batch_size', None)
+        if batch_size is None:                           # called outside forward_train / simple_test: one read, as the reference
+            batch_size = int(batch_idx[-1].item()) + 1 if batch_idx.numel() else 1
+        return batch_size
+
+    def get_fg_mask(self, seg_scores, seg_points, cls_id, batch_inds, gt_bboxes_3d, gt_labels_3d, seg_logits=None):
+        """single_stage_fsd.py:756-797 for one class, over the sampling kernel (without the at-least-one-point rule, as there).
+        The kernel thresholds the library's own sigmoid of the LOGITS: pass them as ``seg_logits`` (``seg_scores`` is not
+        read)."""
+        if seg_logits is None:
+            raise NotImplementedError('get_fg_mask: pass seg_logits= (the kernel decides on the logits; scores alone are not enough)')
+        thr, extra = self._fg_inputs(seg_logits, seg_points, batch_inds, gt_bboxes_3d, gt_labels_3d)
+        pend = FS.fg_sample_launch(seg_logits, None, seg_points, batch_inds, thr, self._num_samples(batch_inds), extra,
+                                   apply_rule=False)
+        return pend.mask[cls_id]
+
+    def sample(self, dict_to_sample, offset, gt_bboxes_3d=None, gt_labels_3d=None, batch_size=None):
+        """single_stage_fsd.py:698-748 over ``fg_sample``: the reference's per-class lists ``seg_points``, ``batch_idx``,
+        ``center_preds``, ``fg_mask_list`` (+ ``src``, ``slot``, ``class_offsets``, ``totals``, ``rule``).  The wide tensors
+        (``seg_logits``, ``seg_vote_preds``, ``seg_feats``) are NOT copied per class here: ``update_sample_results_by_mask``
+        gathers them once, after the cluster filter, from ``source`` (the input dictionary, which rides along).  One host read.
+        The reference's ``assert (seg_logits < 0).any()`` - a device read for a debugging check - is dropped."""
+        if _get(self.cfg, 'group_sample', False):
+            raise NotImplementedError('SingleStageFSD.sample: group_sample (the softmax score path) is not built')
+        seg_logits = dict_to_sample['seg_logits']
+        if seg_logits.size(1) != self.num_classes:
+            raise NotImplementedError('SingleStageFSD.sample: seg_logits with a background column (the softmax score path, '
+                                      'group_sample) is not built')
+        seg_points, batch_idx = dict_to_sample['seg_points'], dict_to_sample['batch_idx']
+        thr, extra = self._fg_inputs(seg_logits, seg_points, batch_idx, gt_bboxes_3d, gt_labels_3d)
+        out = dict(FS.fg_sample(seg_logits, offset, seg_points, batch_idx, thr, self._num_samples(batch_idx, batch_size), extra))
+        out['source'] = dict_to_sample
+        return out
+
+    def update_sample_results_by_mask(self, sampled_out, valid_mask_list):
+        """single_stage_fsd.py:571-586 over ``fg_gather_cat``: the narrow per-class lists are indexed by the assigner's
+        ``valid_mask`` (its ``_sst_keep`` index list: no search), the final masks come from one small launch, and the wide rows
+        of all classes are gathered ONCE into ``combined`` (``pts_feats`` = logits | vote predictions | features, ``seg_points``,
+        ``center_preds``), which ``combine_classes`` hands out.  The reference's ``assert new_data.sum() == mask.sum()`` (a
+        device read) is dropped."""
+        src = sampled_out['source']
+        detach = bool(_get(self.train_cfg, 'detach_segmentor', False)) if self.training else False
+        out = FS.fg_gather_cat(sampled_out, valid_mask_list, src['seg_logits'], src['seg_vote_preds'], src['seg_feats'],
+                               src['seg_points'], detach_feats=detach)
+        keeps = [FS.keep_of(v) if v.dtype == torch.bool else v for v in valid_mask_list]
+        new = dict(sampled_out)
+        for name in ('seg_points', 'batch_idx', 'center_preds'):
+            new[name] = [d[k] for d, k in zip(sampled_out[name], keeps)]
+        n_l, n_v = src['seg_logits'].size(1), src['seg_vote_preds'].size(1)
+        feats = out['pts_feats']
+        new['fg_mask_list'] = out['fg_mask_list']
+        new['slot2'] = out['slot2']
+        new['combined'] = dict(seg_points=out['seg_points'], center_preds=out['center_preds'], pts_feats=feats,
+                               seg_logits=feats[:, :n_l], seg_vote_preds=feats[:, n_l:n_l + n_v], seg_feats=feats[:, n_l + n_v:])
+        return new
+
+    def _cluster_step(self, seg_out_dict, seg_feats, img_metas, gt_bboxes_3d, gt_labels_3d, train):
+        """what forward_train (:508-543) and simple_test (:636-667) share between the segmentor and the box head"""
+        det = (lambda t: t.detach()) if train else (lambda t: t)
+        dict_to_sample = dict(seg_points=seg_out_dict['seg_points'], seg_logits=det(seg_out_dict['seg_logits']),
+                              seg_vote_preds=det(seg_out_dict['seg_vote_preds']), seg_feats=seg_feats,
+                              batch_idx=seg_out_dict['batch_idx'], vote_offsets=det(seg_out_dict['offsets']))
+        if _get(self.cfg, 'pre_voxelization_size', None) is not None:
+            dict_to_sample = self.pre_voxelize(dict_to_sample)
+        sampled_out = self.sample(dict_to_sample, dict_to_sample['vote_offsets'], gt_bboxes_3d, gt_labels_3d)
+        cluster_inds_list, valid_mask_list = self.cluster_assigner(sampled_out['center_preds'], sampled_out['batch_idx'],
+                                                                   gt_bboxes_3d, gt_labels_3d,
+                                                                   origin_points=sampled_out['seg_points'])
+        pts_cluster_inds = torch.cat(cluster_inds_list, dim=0)            # (class, sample, cluster) per point
+        sampled_out = self.update_sample_results_by_mask(sampled_out, valid_mask_list)
+        combined_out = self.combine_classes(sampled_out, ['seg_points', 'pts_feats', 'center_preds'])
+        points, pts_feats = combined_out['seg_points'], combined_out['pts_feats']
+        assert len(pts_cluster_inds) == len(points) == len(pts_feats)
+        extracted_outs = self.extract_feat(points, pts_feats, pts_cluster_inds, img_metas, combined_out['center_preds'])
+        outs = self.bbox_head(extracted_outs['cluster_feats'], extracted_outs['cluster_xyz'], extracted_outs['cluster_inds'])
+        return dict_to_sample, sampled_out, points, extracted_outs, outs
+
+    def forward_train(self, points, img_metas, gt_bboxes_3d, gt_labels_3d, gt_bboxes_ignore=None, runtime_info=None):
+        """single_stage_fsd.py:487-569: points and ground-truth boxes -> the loss dictionary (segmentor losses, num_clusters,
+        num_fg_points, the cluster head's losses), or with ``as_rpn`` the reference's output dictionary for the RoI stage.
+        ``num_clusters`` is the row count of the grouping ``extract_feat`` makes anyway, not a further ``unique``; the
+        reference's asserts that read the device (``(seg_logits < 0).any()``, ``cluster_inds[:, 0].max().item()``) are dropped."""
+        self._require_heads('forward_train')
+        if runtime_info is not None:
+            self.runtime_info = runtime_info
+        losses = {}
+        gt_bboxes_3d = [b[l >= 0] for b, l in zip(gt_bboxes_3d, gt_labels_3d)]
+        gt_labels_3d = [l[l >= 0] for l in gt_labels_3d]
+        self._batch_size = len(points)
+        seg_out_dict = self.segmentor.forward_train(points=points, img_metas=img_metas, gt_bboxes_3d=gt_bboxes_3d,
+                                                    gt_labels_3d=gt_labels_3d, as_subsegmentor=True)
+        seg_feats = seg_out_dict['seg_feats']
+        if _get(self.train_cfg, 'detach_segmentor', False):
+            seg_feats = seg_feats.detach()
+        losses.update(seg_out_dict['losses'])
+        dict_to_sample, sampled_out, fg_points, extracted_outs, outs = self._cluster_step(
+            seg_out_dict, seg_feats, img_metas, gt_bboxes_3d, gt_labels_3d, train=True)
+        cluster_xyz, cluster_inds = extracted_outs['cluster_xyz'], extracted_outs['cluster_inds']
+        dev = fg_points.device
+        losses['num_clusters'] = torch.ones((1,), device=dev).float() * cluster_xyz.size(0)
+        losses['num_fg_points'] = torch.ones((1,), device=dev).float() * len(fg_points)
+        det_loss = self.bbox_head.loss(outs['cls_logits'], outs['reg_preds'], cluster_xyz, cluster_inds, gt_bboxes_3d,
+                                       gt_labels_3d, img_metas, iou_logits=outs.get('iou_logits', None),
+                                       gt_bboxes_ignore=gt_bboxes_ignore)
+        if hasattr(self.bbox_head, 'print_info'):
+            self.print_info.update(self.bbox_head.print_info)
+        losses.update(det_loss)
+        losses.update(self.print_info)
+        if not self.as_rpn:
+            return losses
+        return dict(rpn_losses=losses, cls_logits=outs['cls_logits'], reg_preds=outs['reg_preds'], cluster_xyz=cluster_xyz,
+                    cluster_inds=cluster_inds, all_input_points=dict_to_sample['seg_points'],
+                    valid_pts_feats=extracted_outs['cluster_pts_feats'], valid_pts_xyz=extracted_outs['cluster_pts_xyz'],
+                    seg_feats=dict_to_sample['seg_feats'], pts_mask=sampled_out['fg_mask_list'],
+                    pts_batch_inds=dict_to_sample['batch_idx'])
+
+    def simple_test(self, points, img_metas, imgs=None, rescale=False, gt_bboxes_3d=None, gt_labels_3d=None):
+        """single_stage_fsd.py:621-691 (one sample); the reference's ``assert (cluster_inds[:, 1] == 0).all()`` (a device read)
+        is dropped"""
+        self._require_heads('simple_test')
+        if gt_bboxes_3d is not None:
+            gt_bboxes_3d, gt_labels_3d = gt_bboxes_3d[0], gt_labels_3d[0]
+            assert isinstance(gt_bboxes_3d, list) and isinstance(gt_labels_3d, list)
+            assert len(gt_bboxes_3d) == len(gt_labels_3d) == 1, 'assuming single sample testing'
+            gt_bboxes_3d = [b[l >= 0] for b, l in zip(gt_bboxes_3d, gt_labels_3d)]
+            gt_labels_3d = [l[l >= 0] for l in gt_labels_3d]
+        self._batch_size = len(points)
+        seg_out_dict = self.segmentor.simple_test(points, img_metas)
+        dict_to_sample, sampled_out, _, extracted_outs, outs = self._cluster_step(
+            seg_out_dict, seg_out_dict['seg_feats'], img_metas, gt_bboxes_3d, gt_labels_3d, train=False)
+        bbox_list = self.bbox_head.get_bboxes(outs['cls_logits'], outs['reg_preds'], extracted_outs['cluster_xyz'],
+                                              extracted_outs['cluster_inds'], img_metas, rescale=rescale,
+                                              iou_logits=outs.get('iou_logits', None))
+        if self.as_rpn:
+            return dict(all_input_points=dict_to_sample['seg_points'], valid_pts_feats=extracted_outs['cluster_pts_feats'],
+                        valid_pts_xyz=extracted_outs['cluster_pts_xyz'], seg_feats=dict_to_sample['seg_feats'],
+                        pts_mask=sampled_out['fg_mask_list'], pts_batch_inds=dict_to_sample['batch_idx'],
+                        proposal_list=bbox_list)
+        return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
+
 
 @DETECTORS.register_module()
 class FSD(SingleStageFSD):
@@ -530,6 +737,68 @@ class FSD(SingleStageFSD):
         ext = dict(_get(roi_head, 'roi_extractor', None) or {})
         self.with_virtual = ext.pop('with_virtual', False)
         self.roi_extractor = ROI_EXTRACTORS.build(ext) if ext else None
+
+    def forward_train(self, points, img_metas, gt_bboxes_3d, gt_labels_3d, gt_bboxes_ignore=None):
+        """two_stage_fsd.py:48-106: the first stage as RPN, its boxes as proposals, the RoI input, the RoI head's losses"""
+        self._require_heads('forward_train')
+        gt_bboxes_3d = [b[l >= 0] for b, l in zip(gt_bboxes_3d, gt_labels_3d)]
+        gt_labels_3d = [l[l >= 0] for l in gt_labels_3d]
+        point_drop_ratio = _get(self.train_cfg, 'point_drop_ratio', 0)
+        if point_drop_ratio > 0:
+            kept = []
+            for p in points:
+                idx = torch.randperm(len(p)).to(p.device)
+                kept.append(p[idx[:int(len(p) * (1 - point_drop_ratio))]])
+            points = kept
+        losses = {}
+        rpn_outs = super().forward_train(points=points, img_metas=img_metas, gt_bboxes_3d=gt_bboxes_3d,
+                                         gt_labels_3d=gt_labels_3d, gt_bboxes_ignore=gt_bboxes_ignore,
+                                         runtime_info=self.runtime_info)
+        losses.update(rpn_outs['rpn_losses'])
+        proposal_list = self.bbox_head.get_bboxes(rpn_outs['cls_logits'], rpn_outs['reg_preds'], rpn_outs['cluster_xyz'],
+                                                  rpn_outs['cluster_inds'], img_metas)
+        assert len(proposal_list) == len(gt_bboxes_3d)
+        pts_xyz, pts_feats, pts_batch_inds = self.prepare_multi_class_roi_input(
+            rpn_outs['all_input_points'], rpn_outs['valid_pts_feats'], rpn_outs['seg_feats'], rpn_outs['pts_mask'],
+            rpn_outs['pts_batch_inds'], rpn_outs['valid_pts_xyz'])
+        losses.update(self.roi_head.forward_train(pts_xyz, pts_feats, pts_batch_inds, img_metas, proposal_list, gt_bboxes_3d,
+                                                  gt_labels_3d))
+        return losses
+
+    def _roi_detach(self):
+        return dict(detach_seg_feats=bool(self.training and _get(self.train_cfg, 'detach_seg_feats', False)),
+                    detach_cluster_feats=bool(self.training and _get(self.train_cfg, 'detach_cluster_feats', False)))
+
+    def prepare_roi_input(self, points, cluster_pts_feats, pts_seg_feats, pts_mask, pts_batch_inds, cluster_pts_xyz):
+        """two_stage_fsd.py:108-125 (one class: pad in place) over ``fg_sample.roi_input_single``; the reference's ``isclose``
+        assert on the points (a device read) is dropped"""
+        assert isinstance(pts_mask, list)
+        return FS.roi_input_single(points, cluster_pts_feats, pts_seg_feats, pts_mask[:1], pts_batch_inds, **self._roi_detach())
+
+    def prepare_multi_class_roi_input(self, points, cluster_pts_feats, pts_seg_feats, pts_mask, pts_batch_inds, cluster_pts_xyz):
+        """two_stage_fsd.py:127-178 over ``fg_sample.roi_input``: rows sorted by sample, inside a sample the background points
+        in point order, then class 0, class 1, ... (the stable sort of the reference's concatenation; the reference's
+        ``sort()`` leaves that order open on a GPU).  One host read (the row count); the ``isclose`` assert is dropped."""
+        assert isinstance(pts_mask, list)
+        pts, feats, bidx, _ = FS.roi_input(points, cluster_pts_feats, pts_seg_feats, pts_mask, pts_batch_inds,
+                                           self._num_samples(pts_batch_inds), **self._roi_detach())
+        return pts, feats, bidx
+
+    def simple_test(self, points, img_metas, imgs=None, rescale=False, gt_bboxes_3d=None, gt_labels_3d=None):
+        """two_stage_fsd.py:180-223"""
+        self._require_heads('simple_test')
+        rpn_outs = super().simple_test(points=points, img_metas=img_metas, gt_bboxes_3d=gt_bboxes_3d, gt_labels_3d=gt_labels_3d)
+        proposal_list = rpn_outs['proposal_list']
+        if _get(self.test_cfg, 'skip_rcnn', False):
+            return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in proposal_list]
+        if self.num_classes > 1 or _get(self.test_cfg, 'enable_multi_class_test', False):
+            prepare_func = self.prepare_multi_class_roi_input
+        else:
+            prepare_func = self.prepare_roi_input
+        pts_xyz, pts_feats, pts_batch_inds = prepare_func(
+            rpn_outs['all_input_points'], rpn_outs['valid_pts_feats'], rpn_outs['seg_feats'], rpn_outs['pts_mask'],
+            rpn_outs['pts_batch_inds'], rpn_outs['valid_pts_xyz'])
+        return self.roi_head.simple_test(pts_xyz, pts_feats, pts_batch_inds, img_metas, proposal_list, gt_bboxes_3d, gt_labels_3d)
 
 
 @DETECTORS.register_module()
