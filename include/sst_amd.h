@@ -1823,6 +1823,78 @@ int sst_fg_roi_cat_fwd_f32(const int32_t* d_src, const int32_t* d_row, int64_t r
 int sst_fg_gather_cat_bwd_f32(const float* d_out_grad, int64_t rows, int64_t ld_out, int col0, const int32_t* d_slot2, int64_t n,
                               int num_classes, int feat_cols, float* d_feats_grad, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FSDv2 grouped foreground sampling (csrc/fg_group_sample.hip): the stage between the segmentor and the
+ * virtual voxels.
+ *
+ * sst_fg_group_sample_f32 - replaces SingleStageFSDV2.batched_group_sample / group_sample with get_fg_mask,
+ * gather_group_by_names, get_sample_beg_position and get_offset_weight
+ * (mmdet3d/models/detectors/single_stage_fsd_v2.py:656-705, 726-891) for all groups and all samples of a batch: three launches
+ * and one memset, no host read.  logits [n, num_logits] (K = C + 1 columns, the background among them) go through an fp32
+ * softmax (row maximum subtracted, expf, sum in ascending column order, one division per probability); the score of group g is
+ * the sum of the probabilities of group_class[group_begin[g] .. group_begin[g + 1]) in that order (:879-891);
+ * mask[g][i] = score > thresholds[g] (+inf: never), ORed with extra_mask[g][i] (bool [G, n] or NULL; logits may be NULL when
+ * centers is NULL, then extra_mask alone decides).  batch_idx and the at-least-one-point rule are those of sst_fg_sample_f32
+ * (:820-822; with batch = 1 also `fg_mask[0] = True` of :756-757).  Outputs as there, class after class read as group after
+ * group: slot int32 [G, n], mask bool [G, n], src, batch_out, points_out, and
+ *   centers[row] = points[i][:3] + offset_scale * sum over the group's classes k, in listed order, of votes[i][3k:3k+3] * w_k,
+ *   w_k = (|logits[i][k] - m| < 1e-6f) / (number of such k), m the maximum of the group's logits (:826-839, :855-861);
+ *   every product, quotient and sum is rounded on its own (no fused multiply-add).
+ * info int32 [sst_fg_sample_info_words(G)] = totals[G] | rule[G] | group_off[G + 1] | status.  num_groups <=
+ * SST_FG_MAX_CLASSES and num_logits <= SST_FG_MAX_LOGITS, else SST_ERR_UNSUPPORTED; a class listed twice is SST_ERR_ARG.
+ *
+ * sst_fg_virtual_rows_fwd_f32 - the input rows of the virtual-point projector (SingleStageFSDV2.extract_feat :164-176 with
+ * clip_points :124-129) gathered once through src int32 [m] (the point of every sampled row):
+ *   out [m, c_feats + 3 + c_logits + (c_points - 3)] = (feats[i] | (clip(centers[j]) - points[i][:3]) / 10 | logits[i] |
+ *   points[i][3:]), clipped [m, 3] = clip(centers[j]) = min(max(., lo), hi); an index outside [0, n) gives zeros.  The division
+ *   is one fp32 subtraction and one fp32 product with fl32(1 / 10), as torch divides a device tensor by a scalar.
+ * sst_fg_virtual_rows_bwd_f32 - d_feats_grad[i][f] = sum over the groups in ascending order of
+ * d_out_grad[offsets[g] + slot[g][i]][f] (slot int32 [G, n]: the row within the group or -1; offsets: G + 1 HOST values),
+ * zeros where no group holds the point: every element written, no float atomic.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_FG_MAX_LOGITS 64
+typedef struct sst_fg_group_sample_args {
+  const float* logits;
+  const float* votes;
+  const float* points;
+  const void* batch_idx;
+  const uint8_t* extra_mask;
+  int32_t* slot;
+  uint8_t* mask;
+  int32_t* src;
+  float* centers;
+  void* batch_out;
+  float* points_out;
+  int32_t* info;
+  int64_t n, ld_logits, ld_votes, ld_points, max_rows;
+  int32_t num_groups, num_logits, point_cols, batch, batch_is_i64, apply_rule;
+  float offset_scale;
+  float thresholds[SST_FG_MAX_CLASSES];
+  uint8_t group_begin[SST_FG_MAX_CLASSES + 1];
+  uint8_t group_class[SST_FG_MAX_LOGITS];
+} sst_fg_group_sample_args;
+typedef struct sst_fg_virtual_rows_args {
+  const int32_t* src;
+  const float* centers;
+  const float* feats;
+  const float* logits;
+  const float* points;
+  float* out;
+  float* clipped;
+  int64_t m, n, ld_feats, ld_logits, ld_points;
+  int32_t c_feats, c_logits, c_points, reserved;
+  float lo[3], hi[3];
+} sst_fg_virtual_rows_args;
+typedef struct sst_fg_group_offsets {
+  int64_t off[SST_FG_MAX_CLASSES + 1];
+} sst_fg_group_offsets;
+int64_t sst_fg_group_sample_workspace_bytes(int64_t n, int num_groups, int batch);
+int sst_fg_group_sample_f32(const sst_fg_group_sample_args* args, void* d_workspace, void* stream);
+int sst_fg_virtual_rows_fwd_f32(const sst_fg_virtual_rows_args* args, void* stream);
+int sst_fg_virtual_rows_bwd_f32(const float* d_out_grad, int64_t rows, int64_t ld_out, const int32_t* d_slot,
+                                const sst_fg_group_offsets* offsets, int64_t n, int num_groups, int feat_cols, float* d_feats_grad,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

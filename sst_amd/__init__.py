@@ -55,6 +55,10 @@ from .anchor_head import (ANCHOR_GENERATORS, SECONDFPN, AlignedAnchor3DRangeGene
                           anchor_decode, anchor_loss, anchor_targets, build_anchor_generator)
 from . import fg_sample  # noqa: F401
 from .fg_sample import (fg_gather_cat, fg_sample_launch, roi_input, roi_input_single)  # noqa: F401
+from . import fg_group_sample  # noqa: F401
+from .fg_group_sample import group_sample, group_sample_launch, group_topk_extra_mask, virtual_rows  # noqa: F401
+from . import fsdv2_step  # noqa: F401
+from .fsdv2_step import FSDV2Step, SingleStageFSDV2Step, attach_fsdv2_heads  # noqa: F401
 
 __version__ = '0.1.0'
 
@@ -89,4 +93,6 @@ __all__ = [
     'anchor_head', 'anchor_targets', 'anchor_loss', 'anchor_decode', 'Anchor3DHead', 'SECONDFPN', 'ANCHOR_GENERATORS',
     'Anchor3DRangeGenerator', 'AlignedAnchor3DRangeGenerator', 'build_anchor_generator',
     'fg_sample', 'fg_sample_launch', 'fg_gather_cat', 'roi_input', 'roi_input_single',
+    'fg_group_sample', 'group_sample', 'group_sample_launch', 'group_topk_extra_mask', 'virtual_rows',
+    'fsdv2_step', 'attach_fsdv2_heads', 'SingleStageFSDV2Step', 'FSDV2Step',
 ]

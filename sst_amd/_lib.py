@@ -97,6 +97,19 @@ FgGatherArgs = _struct('FgGatherArgs', 'sst_fg_gather_args of include/sst_amd.h'
     [(k, ctypes.c_void_p) for k in ('idx', 'logits', 'votes', 'feats', 'points', 'out', 'points_out')]
     + [(k, c_i64) for k in ('m', 'n', 'ld_logits', 'ld_votes', 'ld_feats', 'ld_points')]
     + [(k, _I32) for k in ('c_logits', 'c_votes', 'c_feats', 'c_points')]))
+FgGroupSampleArgs = _struct('FgGroupSampleArgs', 'sst_fg_group_sample_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('logits', 'votes', 'points', 'batch_idx', 'extra_mask', 'slot', 'mask', 'src', 'centers',
+                                    'batch_out', 'points_out', 'info')]
+    + [(k, c_i64) for k in ('n', 'ld_logits', 'ld_votes', 'ld_points', 'max_rows')]
+    + [(k, _I32) for k in ('num_groups', 'num_logits', 'point_cols', 'batch', 'batch_is_i64', 'apply_rule')]
+    + [('offset_scale', ctypes.c_float), ('thresholds', ctypes.c_float * 32), ('group_begin', ctypes.c_uint8 * 33),
+       ('group_class', ctypes.c_uint8 * 64)]))
+FgVirtualRowsArgs = _struct('FgVirtualRowsArgs', 'sst_fg_virtual_rows_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('src', 'centers', 'feats', 'logits', 'points', 'out', 'clipped')]
+    + [(k, c_i64) for k in ('m', 'n', 'ld_feats', 'ld_logits', 'ld_points')]
+    + [(k, _I32) for k in ('c_feats', 'c_logits', 'c_points', 'reserved')]
+    + [('lo', ctypes.c_float * 3), ('hi', ctypes.c_float * 3)]))
+FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
 EncoderLayerFwdArgs = _struct('EncoderLayerFwdArgs', 'sst_encoder_layer_fwd_args of include/sst_amd.h', (
@@ -448,6 +461,10 @@ _SIGNATURES = {
     'sst_fg_gather_cat_fwd_f32': (c_i32, [c_ptr, c_ptr]),
     'sst_fg_roi_cat_fwd_f32': (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i64, c_i32, c_ptr, c_ptr]),
     'sst_fg_gather_cat_bwd_f32': (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
+    'sst_fg_group_sample_workspace_bytes': (c_i64, [c_i64, c_i32, c_i32]),
+    'sst_fg_group_sample_f32': (c_i32, [c_ptr, c_ptr, c_ptr]),
+    'sst_fg_virtual_rows_fwd_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_fg_virtual_rows_bwd_f32': (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

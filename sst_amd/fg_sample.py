@@ -80,6 +80,7 @@ class FgSamplePending(object):
         cut = lambda t: [t[off[k]:off[k + 1]] for k in range(c)]
         self._result = dict(seg_points=cut(self.points_out), batch_idx=cut(self.batch_out), center_preds=cut(self.centers),
                             fg_mask_list=list(self.mask.unbind(0)), src=cut(self.src), src_cat=self.src[:off[c]],
+                            center_cat=self.centers[:off[c]], points_cat=self.points_out[:off[c]], batch_cat=self.batch_out[:off[c]],
                             slot=self.slot, class_offsets=off, totals=totals, rule=rule)
         return self._result
 

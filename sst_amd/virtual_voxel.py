@@ -138,10 +138,13 @@ class VirtualVoxelExtractor(nn.Module):
     # ------------------------------------------------------------------------------------------------------------ stage
     def extract_feat(self, sampled_dict, origin_dict, gt_bboxes_3d=None, multiscale_features=None):
         fg_pts, fg_batch = sampled_dict['seg_points'], sampled_dict['batch_idx']
-        centers = self.clip_points(sampled_dict['center_preds'], self.point_cloud_range)   # votes may leave the range
-        offset = (centers - fg_pts[:, :3]) / 10                                             # the reference's normaliser
-        vir_feat = self.virtual_proj(torch.cat([sampled_dict['seg_feats'], offset, sampled_dict['seg_logits'],
-                                                fg_pts[:, 3:]], 1))
+        if 'virtual_input' in sampled_dict:    # the projector's rows and the clipped centres as one gather wrote them (fg_group_sample.virtual_rows)
+            centers, vir_in = sampled_dict['center_preds'], sampled_dict['virtual_input']
+        else:
+            centers = self.clip_points(sampled_dict['center_preds'], self.point_cloud_range)   # votes may leave the range
+            offset = (centers - fg_pts[:, :3]) / 10                                             # the reference's normaliser
+            vir_in = torch.cat([sampled_dict['seg_feats'], offset, sampled_dict['seg_logits'], fg_pts[:, 3:]], 1)
+        vir_feat = self.virtual_proj(vir_in)
         if self.zero_virtual_feature:
             vir_feat = vir_feat * 0
         ori_pts = origin_dict['seg_points']
