@@ -1895,6 +1895,37 @@ int sst_fg_virtual_rows_bwd_f32(const float* d_out_grad, int64_t rows, int64_t l
                                 const sst_fg_group_offsets* offsets, int64_t n, int num_groups, int feat_cols, float* d_feats_grad,
                                 void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Deformable convolution v1 (csrc/deform_conv.hip), fp32, NCHW, everything on `stream`, no float atomics: two runs agree bit
+ * for bit.  The operator of mmcv's deform_conv2d (DCN of CenterHead's DCNSeparateHead, centerpoint_head.py:123-239), restated
+ * from its published kernel; nothing compiled from mmcv was available to compare with.
+ *   input [B, Cin, H, W], offset [B, deform_groups * 2 * kh * kw, Ho, Wo], weight [Cout, Cin / groups, kh, kw],
+ *   out [B, Cout, Ho, Wo], Ho = (H + 2 pad_h - (dil_h (kh - 1) + 1)) / stride_h + 1, Wo likewise.
+ *   For output pixel (ho, wo) and tap (i, j): h = ho stride_h - pad_h + i dil_h + off_h, w = wo stride_w - pad_w + j dil_w + off_w,
+ *   off_h = channel 2 (i kw + j) and off_w = channel 2 (i kw + j) + 1 of the block of deformable group c / (Cin / deform_groups).
+ *   The sample is 0 unless h > -1 && w > -1 && h < H && w < W, otherwise the bilinear value over the cell (floor(h), floor(w))
+ *   with corners outside the image contributing 0.  Column order c kh kw + i kw + j; no bias, no modulation mask.  The
+ *   derivative in an offset is that of the cell floor() selects, and 0 where the sample is 0.
+ * Forward: one launch, no workspace.  Backward: d_workspace of sst_deform_conv_bwd_workspace_bytes(shape) bytes (an int64 image
+ * of the input for the order-independent fixed-point sum of the input gradient, and one weight partial per block of the weight
+ * gradient's grid: sst_deform_conv_wgrad_blocks(tiles) blocks, block x taking the tiles x, x + blocks, ...; a tile is
+ * sst_deform_conv_tile_pixels() consecutive output pixels of one sample).  All three gradients are always written.
+ * kh, kw <= 3 and Ho Wo kh kw <= 2^22 in the backward, else SST_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sst_deform_conv_shape {
+  int32_t batch, in_channels, height, width, out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w,
+      groups, deform_groups, reserved;
+} sst_deform_conv_shape;
+int sst_deform_conv_tile_pixels(void);
+int sst_deform_conv_wgrad_blocks(int64_t total_tiles);
+int sst_deform_conv_out_size(const sst_deform_conv_shape* shape, int32_t* out_h, int32_t* out_w);
+int64_t sst_deform_conv_bwd_workspace_bytes(const sst_deform_conv_shape* shape);
+int sst_deform_conv_fwd_f32(const sst_deform_conv_shape* shape, const float* d_input, const float* d_offset,
+                            const float* d_weight, float* d_out, void* stream);
+int sst_deform_conv_bwd_f32(const sst_deform_conv_shape* shape, const float* d_input, const float* d_offset,
+                            const float* d_weight, const float* d_out_grad, float* d_input_grad, float* d_offset_grad,
+                            float* d_weight_grad, void* d_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

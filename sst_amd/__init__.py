@@ -59,6 +59,9 @@ from . import fg_group_sample  # noqa: F401
 from .fg_group_sample import group_sample, group_sample_launch, group_topk_extra_mask, virtual_rows  # noqa: F401
 from . import fsdv2_step  # noqa: F401
 from .fsdv2_step import FSDV2Step, SingleStageFSDV2Step, attach_fsdv2_heads  # noqa: F401
+from . import deform_conv  # noqa: F401
+from .deform_conv import (DeformConv2d, DeformConv2dPack, deform_conv2d, deform_conv_tile_pixels,  # noqa: F401
+                          deform_conv_wgrad_blocks)
 
 __version__ = '0.1.0'
 
@@ -95,4 +98,5 @@ __all__ = [
     'fg_sample', 'fg_sample_launch', 'fg_gather_cat', 'roi_input', 'roi_input_single',
     'fg_group_sample', 'group_sample', 'group_sample_launch', 'group_topk_extra_mask', 'virtual_rows',
     'fsdv2_step', 'attach_fsdv2_heads', 'SingleStageFSDV2Step', 'FSDV2Step',
+    'deform_conv', 'deform_conv2d', 'DeformConv2d', 'DeformConv2dPack', 'deform_conv_tile_pixels', 'deform_conv_wgrad_blocks',
 ]

@@ -109,6 +109,9 @@ FgVirtualRowsArgs = _struct('FgVirtualRowsArgs', 'sst_fg_virtual_rows_args of in
     + [(k, c_i64) for k in ('m', 'n', 'ld_feats', 'ld_logits', 'ld_points')]
     + [(k, _I32) for k in ('c_feats', 'c_logits', 'c_points', 'reserved')]
     + [('lo', ctypes.c_float * 3), ('hi', ctypes.c_float * 3)]))
+DeformConvShape = _struct('DeformConvShape', 'sst_deform_conv_shape of include/sst_amd.h', [
+    (k, _I32) for k in ('batch', 'in_channels', 'height', 'width', 'out_channels', 'kernel_h', 'kernel_w', 'stride_h', 'stride_w',
+                        'pad_h', 'pad_w', 'dil_h', 'dil_w', 'groups', 'deform_groups', 'reserved')])
 FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
@@ -465,6 +468,12 @@ _SIGNATURES = {
     'sst_fg_group_sample_f32': (c_i32, [c_ptr, c_ptr, c_ptr]),
     'sst_fg_virtual_rows_fwd_f32': (c_i32, [c_ptr, c_ptr]),
     'sst_fg_virtual_rows_bwd_f32': (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
+    'sst_deform_conv_tile_pixels': (c_i32, []),
+    'sst_deform_conv_wgrad_blocks': (c_i32, [c_i64]),
+    'sst_deform_conv_out_size': (c_i32, [c_ptr, c_ptr, c_ptr]),
+    'sst_deform_conv_bwd_workspace_bytes': (c_i64, [c_ptr]),
+    'sst_deform_conv_fwd_f32': (c_i32, [c_ptr] * 6),
+    'sst_deform_conv_bwd_f32': (c_i32, [c_ptr] * 10),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

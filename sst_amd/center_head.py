@@ -7,9 +7,11 @@ fill and two launches backward, no ``.item()``, no permuted copy of the regressi
 :612-830, and CenterPointBBoxCoder of mmdet3d/core/bbox/coders/centerpoint_bbox_coders.py (``center_decode``: torch.topk as
 ``_topk`` composes it, then one launch gathering straight from the NCHW maps).
 
-The head's network (shared convolution, SeparateHead / DCNSeparateHead), SECONDFPN and circle NMS are not built: CenterHead keeps
-their configs in ``self.unbuilt`` and ``forward`` raises.  fp32 device tensors only; CPU tensors raise.
+The head's network (the shared convolution and SeparateHead / DCNSeparateHead, :18-239, the latter over the deformable
+convolution of sst_amd/deform_conv.py) is opt-in: CenterHead keeps its configs in ``self.unbuilt`` and ``forward`` raises until
+``attach_network()`` builds it.  Circle NMS is not built.  fp32 device tensors only; CPU tensors raise.
 """
+import copy
 import ctypes
 import functools
 
@@ -19,7 +21,8 @@ from torch import nn
 from . import _head_common
 from . import _lib
 from . import box_ops
-from .detectors import HEADS
+from .detectors import HEADS, build_head
+from .norm import build_conv_layer, build_norm_layer
 from .registry import Registry
 
 BBOX_CODERS = Registry('bbox_coder')  # mmdet.core.bbox.builder.BBOX_CODERS
@@ -299,17 +302,104 @@ class CenterPointBBoxCoder(object):
                 for i in range(heat.size(0))]
 
 
+class ConvModule(nn.Module):
+    """mmcv.cnn.ConvModule as the head uses it: ``conv`` -> ``bn`` (the norm's mmcv name) -> ReLU; ``bias='auto'`` gives the
+    convolution no bias in front of a norm"""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias='auto', conv_cfg=None, norm_cfg=None):
+        super().__init__()
+        if bias == 'auto':
+            bias = norm_cfg is None
+        self.conv = build_conv_layer(conv_cfg, in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=bias)
+        self.norm_name = None
+        if norm_cfg is not None:
+            self.norm_name, norm = build_norm_layer(norm_cfg, out_channels)
+            self.add_module(self.norm_name, norm)
+        self.activate = nn.ReLU(inplace=True)
+
+    def forward(self, x):
+        x = self.conv(x)
+        if self.norm_name is not None:
+            x = getattr(self, self.norm_name)(x)
+        return self.activate(x)
+
+
+@HEADS.register_module()
+class SeparateHead(nn.Module):
+    """centerpoint_head.py:18-120: per head name a Sequential of (num_conv - 1) ConvModules and a biased convolution.
+    Initialisation: torch's Kaiming defaults, the heatmap's last bias ``init_bias`` (parity with mmcv's initialisers is not
+    claimed)."""
+
+    def __init__(self, in_channels, heads, head_conv=64, final_kernel=1, init_bias=-2.19, conv_cfg=dict(type='Conv2d'),
+                 norm_cfg=dict(type='BN2d'), bias='auto', init_cfg=None, **kwargs):
+        assert init_cfg is None, 'To prevent abnormal initialization behavior, init_cfg is not allowed to be set'
+        super().__init__()
+        self.heads = heads
+        self.init_bias = init_bias
+        for head in self.heads:
+            classes, num_conv = self.heads[head]
+            layers, c_in = [], in_channels
+            for _ in range(num_conv - 1):
+                layers.append(ConvModule(c_in, head_conv, kernel_size=final_kernel, stride=1, padding=final_kernel // 2, bias=bias,
+                                         conv_cfg=conv_cfg, norm_cfg=norm_cfg))
+                c_in = head_conv
+            layers.append(build_conv_layer(conv_cfg, head_conv, classes, kernel_size=final_kernel, stride=1,
+                                           padding=final_kernel // 2, bias=True))
+            setattr(self, head, nn.Sequential(*layers))
+        self.init_weights()
+
+    def init_weights(self):
+        for head in self.heads:
+            if head == 'heatmap':
+                getattr(self, head)[-1].bias.data.fill_(self.init_bias)
+
+    def forward(self, x):
+        return {head: getattr(self, head)(x) for head in self.heads}
+
+
+@HEADS.register_module()
+class DCNSeparateHead(nn.Module):
+    """centerpoint_head.py:123-239: a deformable convolution in front of the heatmap head and another in front of the
+    regression heads (``feature_adapt_cls`` / ``feature_adapt_reg``), ``cls_head`` and the SeparateHead ``task_head``.  As in the
+    reference, ``task_head`` is built with SeparateHead's default conv / norm configs.  ``conv_offset`` starts at zero and
+    the heatmap's last bias at ``init_bias``; everything else has torch's Kaiming defaults."""
+
+    def __init__(self, in_channels, num_cls, heads, dcn_config, head_conv=64, final_kernel=1, init_bias=-2.19,
+                 conv_cfg=dict(type='Conv2d'), norm_cfg=dict(type='BN2d'), bias='auto', init_cfg=None, **kwargs):
+        assert init_cfg is None, 'To prevent abnormal initialization behavior, init_cfg is not allowed to be set'
+        super().__init__()
+        heads = {k: v for k, v in heads.items() if k != 'heatmap'}
+        self.feature_adapt_cls = build_conv_layer(dcn_config)
+        self.feature_adapt_reg = build_conv_layer(dcn_config)
+        self.cls_head = nn.Sequential(
+            ConvModule(in_channels, head_conv, kernel_size=3, padding=1, conv_cfg=conv_cfg, bias=bias, norm_cfg=norm_cfg),
+            build_conv_layer(conv_cfg, head_conv, num_cls, kernel_size=3, stride=1, padding=1, bias=bool(bias)))
+        self.init_bias = init_bias
+        self.task_head = SeparateHead(in_channels, heads, head_conv=head_conv, final_kernel=final_kernel, bias=bias)
+        self.init_weights()
+
+    def init_weights(self):
+        self.cls_head[-1].bias.data.fill_(self.init_bias)
+
+    def forward(self, x):
+        center_feat = self.feature_adapt_cls(x)
+        reg_feat = self.feature_adapt_reg(x)
+        ret = self.task_head(reg_feat)
+        ret['heatmap'] = self.cls_head(center_feat)
+        return ret
+
+
 _NETWORK_KEYS = ('in_channels', 'common_heads', 'separate_head', 'share_conv_channel', 'num_heatmap_convs', 'conv_cfg',
                  'norm_cfg', 'bias')
 
 
 @HEADS.register_module()
 class CenterHead(nn.Module):
-    """CenterHead (dense_heads/centerpoint_head.py:241-830) without its network: targets, losses and box extraction on the
-    kernels of csrc/center_head.hip.  The keys of the shared convolution and the task heads (SeparateHead / DCNSeparateHead)
-    are kept in ``self.unbuilt``; ``forward`` raises.  ``loss`` and ``get_bboxes`` take the ``preds_dicts`` the reference's
-    forward would give: per task a one-element list with a dict of ``heatmap`` / ``reg`` / ``height`` / ``dim`` / ``rot`` /
-    ``vel`` maps."""
+    """CenterHead (dense_heads/centerpoint_head.py:241-830): targets, losses and box extraction on the kernels of
+    csrc/center_head.hip.  The keys of the shared convolution and the task heads (SeparateHead / DCNSeparateHead) are kept in
+    ``self.unbuilt`` and ``forward`` raises until ``attach_network()`` builds them (``shared_conv``, ``task_heads``, the
+    reference's sub-module names).  ``loss`` and ``get_bboxes`` take the ``preds_dicts`` the forward gives: per task a
+    one-element list with a dict of ``heatmap`` / ``reg`` / ``height`` / ``dim`` / ``rot`` / ``vel`` maps."""
 
     def __init__(self, in_channels=[128], tasks=None, train_cfg=None, test_cfg=None, bbox_coder=None, common_heads=dict(),
                  loss_cls=dict(type='GaussianFocalLoss', reduction='mean'),
@@ -340,10 +430,39 @@ class CenterHead(nn.Module):
         self.loss_weight_cls = float(loss_cls.get('loss_weight', 1.0))
         self.loss_weight_bbox = float(loss_bbox.get('loss_weight', 1.0))
 
+    def attach_network(self):
+        """Opt in to the head's network: build ``shared_conv`` and ``task_heads`` from ``self.unbuilt`` (:310-327) -> self.
+        ``unbuilt`` stays as it is; a head without this call has no parameters and ``forward`` raises."""
+        u = self.unbuilt
+        in_channels = u['in_channels']
+        if isinstance(in_channels, (list, tuple)):
+            if len(in_channels) != 1:
+                raise NotImplementedError(f'CenterHead.attach_network: in_channels {in_channels}: one feature level is built')
+            in_channels = in_channels[0]
+        self.shared_conv = ConvModule(in_channels, u['share_conv_channel'], kernel_size=3, padding=1, conv_cfg=u['conv_cfg'],
+                                      norm_cfg=u['norm_cfg'], bias=u['bias'])
+        self.task_heads = nn.ModuleList()
+        for num_cls in self.num_classes:
+            heads = copy.deepcopy(dict(u['common_heads']))
+            heads.update(dict(heatmap=(num_cls, u['num_heatmap_convs'])))
+            cfg = copy.deepcopy(dict(u['separate_head']))
+            cfg.update(in_channels=u['share_conv_channel'], heads=heads, num_cls=num_cls)
+            self.task_heads.append(build_head(cfg))
+        return self
+
+    def forward_single(self, x):
+        x = self.shared_conv(_lib.as_fp32(x))
+        return [task(x) for task in self.task_heads]
+
     def forward(self, feats):
-        raise NotImplementedError('CenterHead.forward: the shared convolution and the task heads '
-                                  f'({self.unbuilt["separate_head"].get("type")}) are not built; sst_amd.CenterHead covers '
-                                  'get_targets, loss and get_bboxes on the maps those heads produce')
+        if getattr(self, 'task_heads', None) is None:
+            raise NotImplementedError('CenterHead.forward: the shared convolution and the task heads '
+                                      f'({self.unbuilt["separate_head"].get("type")}) are not built; sst_amd.CenterHead covers '
+                                      'get_targets, loss and get_bboxes on the maps those heads produce')
+        if torch.is_tensor(feats):
+            feats = [feats]
+        # multi_apply(self.forward_single, feats): per task the list over the feature levels
+        return tuple(map(list, zip(*[self.forward_single(x) for x in feats])))
 
     def get_targets(self, gt_bboxes_3d, gt_labels_3d):
         return center_targets(gt_bboxes_3d, gt_labels_3d, self.tasks, self.train_cfg, self.norm_bbox)

@@ -350,7 +350,9 @@ class DynamicVoxelNet(nn.Module):
     ``model = dict(type='DynamicVoxelNet', voxel_layer=..., voxel_encoder=..., middle_encoder=..., backbone=..., neck=...,
     bbox_head=...)`` of configs/sst_refactor/*.py constructs up to the backbone's output, with the reference's constructor
     arguments and sub-module names (-> ``state_dict`` keys ``voxel_encoder.*``, ``backbone.*``).  The dense BEV neck (SECOND
-    FPN) and the box head are SURVEY.md section 2 OUT-OF-SCOPE: their configs are kept under ``self.unbuilt``, never run.
+    FPN) and the box head are opt-in: their configs are kept under ``self.unbuilt`` until ``attach_heads()`` builds them as
+    ``neck`` / ``bbox_head``; then ``forward_train`` and ``simple_test`` follow the reference (VoxelNet's), before that they
+    raise.
 
     ``extract_feat`` has the reference's semantics (:38-47: voxelize -> voxel_encoder -> middle_encoder(.., batch_size) ->
     backbone).  When the three index stages are the ones the fused frame plan covers (csrc/frame_plan.hip: DynamicVFE +
@@ -372,7 +374,7 @@ class DynamicVoxelNet(nn.Module):
         self.fused_index = True
         self._planner = None
 
-    with_neck = False          # the dense neck is not built (out of scope): extract_feat ends at the backbone's output
+    with_neck = False          # until attach_heads() builds the dense neck, extract_feat ends at the backbone's output
 
     @torch.no_grad()
     def voxelize(self, points):
@@ -427,6 +429,8 @@ class DynamicVoxelNet(nn.Module):
 
     def extract_feat(self, points, img_metas=None, prepared=None):
         x = self.backbone(self.voxel_info(points, prepared))
+        if self.with_neck:
+            x = self.neck(x)
         return x
 
     def extract_voxel_feats(self, points, img_metas=None, prepared=None):
@@ -437,15 +441,67 @@ class DynamicVoxelNet(nn.Module):
 
     forward = extract_feat
 
+    def attach_heads(self):
+        """Opt in to the training and test steps: build the neck and the box head whose configs are parked in ``self.unbuilt``
+        (``build_neck(unbuilt['neck'])``, ``build_head(dict(unbuilt['bbox_head'], train_cfg=.., test_cfg=..))`` followed by the
+        head's ``attach_network()`` where it has one) and let ``extract_feat`` end at the neck, as dynamic_voxelnet.py:38-47
+        does.  ``unbuilt`` stays as it is; a detector without this call constructs and behaves exactly as before.  Written
+        against ``self`` = any detector object with ``unbuilt`` / ``train_cfg`` / ``test_cfg``.  -> self"""
+        if 'bbox_head' not in self.unbuilt:
+            raise RuntimeError(f'{type(self).__name__}.attach_heads: the config has no bbox_head')
+        if 'neck' in self.unbuilt:
+            self.neck = build_neck(self.unbuilt['neck'])
+            self.with_neck = True
+        head = build_head(dict(self.unbuilt['bbox_head'], train_cfg=self.train_cfg, test_cfg=self.test_cfg))
+        if hasattr(head, 'attach_network'):
+            head.attach_network()
+        self.bbox_head = head
+        return self
+
+    def _require_heads(self, what):
+        if getattr(self, 'bbox_head', None) is None:
+            raise NotImplementedError(f'{type(self).__name__}.{what}: the box head, its losses and target assignment are not built '
+                                      '- call attach_heads() first (the detector parks the neck\'s and the head\'s configs in '
+                                      '`unbuilt` until then)')
+
+    def forward_train(self, points, img_metas, gt_bboxes_3d, gt_labels_3d, gt_bboxes_ignore=None):
+        """VoxelNet.forward_train (detectors/voxelnet.py): bbox_head.loss(*outs, gt_bboxes_3d, gt_labels_3d, img_metas, ..)"""
+        self._require_heads('forward_train')
+        x = self.extract_feat(points, img_metas)
+        outs = self.bbox_head(x)
+        return self.bbox_head.loss(*outs, gt_bboxes_3d, gt_labels_3d, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+
+    def simple_test(self, points, img_metas, imgs=None, rescale=False):
+        """VoxelNet.simple_test: bbox_head.get_bboxes(*outs, img_metas) -> bbox3d2result per sample"""
+        self._require_heads('simple_test')
+        x = self.extract_feat(points, img_metas)
+        outs = self.bbox_head(x)
+        bbox_list = self.bbox_head.get_bboxes(*outs, img_metas, rescale=rescale)
+        return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
+
+    def aug_test(self, *args, **kwargs):
+        raise NotImplementedError(f'{type(self).__name__}.aug_test: test-time augmentation is not built')
+
     def losses(self, *args, **kwargs):
         raise NotImplementedError('the box head, its losses and target assignment are outside the hot path (SURVEY.md section 8)')
-
-    forward_train = simple_test = aug_test = losses
 
 
 @DETECTORS.register_module()
 class DynamicCenterPoint(DynamicVoxelNet):
-    """dynamic_voxelnet.py:73-110: same feature path, CenterHead on top (not built)"""
+    """dynamic_voxelnet.py:73-136: the same feature path with CenterHead on top; the steps after ``attach_heads()``"""
+
+    def forward_train(self, points, img_metas, gt_bboxes_3d, gt_labels_3d, gt_bboxes_ignore=None):
+        self._require_heads('forward_train')
+        x = self.extract_feat(points, img_metas)
+        outs = self.bbox_head(x)
+        return self.bbox_head.loss(gt_bboxes_3d, gt_labels_3d, outs)
+
+    def simple_test(self, points, img_metas, imgs=None, rescale=False):
+        self._require_heads('simple_test')
+        x = self.extract_feat(points, img_metas)
+        outs = self.bbox_head(x)
+        bbox_list = self.bbox_head.get_bboxes(outs, img_metas, rescale=rescale)
+        return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
 
 
 def install_fused_extract_feat(detector_cls):
@@ -466,6 +522,11 @@ def install_fused_extract_feat(detector_cls):
     extract_feat.__doc__ = 'Extract features from points (sst_amd: fused index plan in front of the backbone).'
     detector_cls.extract_feat = extract_feat
     return detector_cls
+
+
+def bbox3d2result(bboxes, scores, labels):
+    """mmdet3d.core.bbox3d2result: the results of one sample on the host"""
+    return dict(boxes_3d=bboxes.to('cpu'), scores_3d=scores.cpu(), labels_3d=labels.cpu())
 
 
 class _HotPathDetector(nn.Module):
@@ -510,11 +571,6 @@ class _HotPathDetector(nn.Module):
         if getattr(self, 'bbox_head', None) is None or ('roi_head' in self.unbuilt and getattr(self, 'roi_head', None) is None):
             raise RuntimeError(f'{type(self).__name__}.{what}: the heads are not built - call attach_heads() first (the detector '
                                'parks their configs in `unbuilt` until then)')
-
-
-def bbox3d2result(bboxes, scores, labels):
-    """mmdet3d.core.bbox3d2result: the results of one sample on the host"""
-    return dict(boxes_3d=bboxes.to('cpu'), scores_3d=scores.cpu(), labels_3d=labels.cpu())
 
 
 @DETECTORS.register_module()

@@ -12,6 +12,7 @@ every reference .py file stays as it is, only the compiled extensions are swappe
     sys.modules['torchex'] = shims.torchex                                      # TorchEx, lidar_box3d.py:5-12
     sys.modules['mmdet3d.ops.furthest_point_sample.furthest_point_sample_ext'] = shims.furthest_point_sample_ext
                                                                                 # furthest_point_sample.py:4, 32-33, 67-68
+    sys.modules['mmcv.ops.deform_conv'] = shims.mmcv_deform_conv                # mmcv's 'DCN': centerpoint_head.py:168-170
 
 Each namespace has exactly the functions, argument orders and in / out conventions of the module it stands for (outputs
 the reference pre-allocates are written in place).  Everything runs on the GPU through the C ABI of libsst_amd.so
@@ -24,6 +25,7 @@ import torch
 
 from . import _lib
 from . import box_ops as _box
+from . import deform_conv as _dcn
 from . import fps as _fps
 from . import kernels as K
 from . import spconv as _spconv
@@ -236,6 +238,21 @@ def _fps_with_dist_wrapper(b, n, m, points_tensor, temp_tensor, idx_tensor):
 
 furthest_point_sample_ext = types.SimpleNamespace(furthest_point_sampling_wrapper=_fps_wrapper,
                                                   furthest_point_sampling_with_dist_wrapper=_fps_with_dist_wrapper)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# mmcv.ops.deform_conv: the function and the two modules ('DCN' of mmcv's CONV_LAYERS is DeformConv2dPack).  mmcv's
+# deform_conv2d takes (input, offset, weight, stride, padding, dilation, groups, deform_groups, bias=False, im2col_step=32):
+# im2col_step only sizes mmcv's column buffer, which this operator does not have
+# ------------------------------------------------------------------------------------------------------------------
+def _deform_conv2d(input, offset, weight, stride=1, padding=0, dilation=1, groups=1, deform_groups=1, bias=False, im2col_step=32):
+    if bias:
+        raise NotImplementedError('deform_conv2d: bias=True is not built')
+    return _dcn.deform_conv2d(input, offset, weight, stride, padding, dilation, groups, deform_groups)
+
+
+mmcv_deform_conv = types.SimpleNamespace(deform_conv2d=_deform_conv2d, DeformConv2d=_dcn.DeformConv2d,
+                                         DeformConv2dPack=_dcn.DeformConv2dPack)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -322,6 +322,11 @@ def build_conv_layer(cfg, *args, **kwargs):
     cfg_ = dict(type='Conv2d') if cfg is None else dict(cfg)
     layer_type = cfg_.pop('type')
     convs = {'Conv1d': nn.Conv1d, 'Conv2d': nn.Conv2d, 'Conv3d': nn.Conv3d, 'Conv': nn.Conv2d}
+    if layer_type in ('DCN', 'DCNv2'):     # mmcv registers DeformConv2dPack / ModulatedDeformConv2dPack under these names
+        from . import deform_conv
+        if layer_type == 'DCNv2':
+            deform_conv._refuse_dcnv2()
+        return deform_conv.DeformConv2dPack(*args, **kwargs, **cfg_)
     if layer_type not in convs:
         from .spconv import CONV_LAYERS  # sparse layers register there as they do in mmcv.cnn.CONV_LAYERS
         sparse = CONV_LAYERS.get(layer_type)
