@@ -1926,6 +1926,67 @@ int sst_deform_conv_bwd_f32(const sst_deform_conv_shape* shape, const float* d_i
                             const float* d_weight, const float* d_out_grad, float* d_input_grad, float* d_offset_grad,
                             float* d_weight_grad, void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The training update (csrc/optim.hip), fp32: what the reference's runner does through mmcv's OptimizerHook /
+ * Fp16OptimizerHook and torch.optim.AdamW after the backward pass.  At most three launches on `stream` for ALL tensors, no host
+ * read, no device allocation, no float atomics: two runs agree bit for bit.
+ *   d_tensors [n_tensors]: one entry per tensor that has a gradient this step.  p and g at any 4-byte aligned address; m and
+ *     v (the optimizer's moments) likewise, 16-byte accesses are used for a chunk whose four addresses allow them and give the
+ *     same bits as the 4-byte path.  group < hyper->n_groups; slot = index of the tensor's step counter in d_steps.
+ *   d_chunks [n_chunks]: the tensors cut into slices of at most sst_optim_chunk_elems() elements, `start` a multiple of it,
+ *     in any fixed order (the order is part of the sum's order).  A tensor of numel 0 has an entry and no chunk.
+ *   hyper: by value per call.  lr, wd, b1, b2, eps per group; max_norm < 0 = no clipping; scale_mode SST_OPTIM_SCALE_*;
+ *     skip_nonfinite != 0: a step whose gradients hold an inf or NaN writes no p, m, v and moves no counter.
+ *   d_steps: fp32 step counters (torch's own type for `step`: exact to 2^24), advanced for the listed tensors only.
+ *   d_record: sst_optim_record_bytes() bytes, 8-byte aligned, kept by the caller between calls:
+ *     double total_norm @0 | float clip_coef @8 | float inv_scale @12 (the one this step used) | float scale @16 (after this
+ *     step's bookkeeping; the caller initialises it, 1 without loss scaling) | int32 found_inf @20 | int32 growth_tracker @24 |
+ *     int32 skipped_steps @28 (running count) | double clip_coef @32 and double inv_scale @40 as the update uses them | reserved.
+ *   d_workspace: sst_optim_workspace_bytes(n_tensors) bytes.
+ * Arithmetic per element, in this order, evaluated in fp64 on the fp32 operands with fp64 scalars and rounded to fp32 once
+ * per result, so that p, m and v are the correctly rounded values of the float64 restatement (half an fp32 ulp):
+ *     g = g * inv_scale * clip_coef;  p = p * (1 - lr wd);  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;
+ *     p = p - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ *   total_norm = sqrt(fp64 sum of (g * inv_scale)^2), clip_coef = min(1, max_norm / (total_norm + 1e-6)); the scale follows
+ *   torch.amp.GradScaler.update.
+ * sst_optim_step_f32 replaces GradScaler.unscale_ + clip_grad_norm_ + AdamW.step + GradScaler.update.
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer, a negative count, n_groups outside
+ * 1..SST_OPTIM_MAX_GROUPS or an unknown scale_mode; SST_ERR_UNSUPPORTED for n_tensors above 2^31 - 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_OPTIM_MAX_GROUPS 8
+#define SST_OPTIM_SCALE_NONE 0     /* no loss scale: inv_scale = 1, the record's scale is neither read nor written */
+#define SST_OPTIM_SCALE_FIXED 1    /* the record's scale is used and never changed (Fp16OptimizerHook)    */
+#define SST_OPTIM_SCALE_DYNAMIC 2  /* GradScaler: backoff on a not-finite step, growth after an interval  */
+typedef struct sst_optim_tensor {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int64_t numel;
+  int32_t group, slot;
+} sst_optim_tensor;
+typedef struct sst_optim_chunk {
+  int64_t start;
+  int32_t tensor, count;
+} sst_optim_chunk;
+typedef struct sst_optim_hyper {
+  double lr[SST_OPTIM_MAX_GROUPS], wd[SST_OPTIM_MAX_GROUPS], b1[SST_OPTIM_MAX_GROUPS], b2[SST_OPTIM_MAX_GROUPS],
+      eps[SST_OPTIM_MAX_GROUPS];
+  double max_norm, growth_factor, backoff_factor;
+  int32_t growth_interval, scale_mode, skip_nonfinite, n_groups;
+} sst_optim_hyper;
+/* elements per chunk (replaces nothing: the layout constant of d_chunks) */
+int sst_optim_chunk_elems(void);
+/* SST_OPTIM_MAX_GROUPS as the library was built (replaces nothing) */
+int sst_optim_max_groups(void);
+/* bytes of the device record (replaces GradScaler's _scale / _growth_tracker / found_inf tensors) */
+int sst_optim_record_bytes(void);
+/* bytes of the per-call workspace (replaces the per-step temporaries of clip_grad_norm_ and the foreach AdamW) */
+int64_t sst_optim_workspace_bytes(int64_t n_tensors);
+/* the update (replaces GradScaler.unscale_ + clip_grad_norm_ + AdamW.step + GradScaler.update) */
+int sst_optim_step_f32(const sst_optim_tensor* d_tensors, int64_t n_tensors, const sst_optim_chunk* d_chunks, int64_t n_chunks,
+                       const sst_optim_hyper* hyper, float* d_steps, void* d_record, void* d_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,9 @@ from .fsdv2_step import FSDV2Step, SingleStageFSDV2Step, attach_fsdv2_heads  # n
 from . import deform_conv  # noqa: F401
 from .deform_conv import (DeformConv2d, DeformConv2dPack, deform_conv2d, deform_conv_tile_pixels,  # noqa: F401
                           deform_conv_wgrad_blocks)
+from . import optim  # noqa: F401
+from .optim import (CyclicLr, CyclicMomentum, FusedAdamW, TrainingUpdate, build_optimizer,  # noqa: F401
+                    build_training_update)
 
 __version__ = '0.1.0'
 
@@ -99,4 +102,5 @@ __all__ = [
     'fg_group_sample', 'group_sample', 'group_sample_launch', 'group_topk_extra_mask', 'virtual_rows',
     'fsdv2_step', 'attach_fsdv2_heads', 'SingleStageFSDV2Step', 'FSDV2Step',
     'deform_conv', 'deform_conv2d', 'DeformConv2d', 'DeformConv2dPack', 'deform_conv_tile_pixels', 'deform_conv_wgrad_blocks',
+    'optim', 'FusedAdamW', 'TrainingUpdate', 'CyclicLr', 'CyclicMomentum', 'build_optimizer', 'build_training_update',
 ]

@@ -112,6 +112,10 @@ FgVirtualRowsArgs = _struct('FgVirtualRowsArgs', 'sst_fg_virtual_rows_args of in
 DeformConvShape = _struct('DeformConvShape', 'sst_deform_conv_shape of include/sst_amd.h', [
     (k, _I32) for k in ('batch', 'in_channels', 'height', 'width', 'out_channels', 'kernel_h', 'kernel_w', 'stride_h', 'stride_w',
                         'pad_h', 'pad_w', 'dil_h', 'dil_w', 'groups', 'deform_groups', 'reserved')])
+OptimHyper = _struct('OptimHyper', 'sst_optim_hyper of include/sst_amd.h', (
+    [(k, ctypes.c_double * 8) for k in ('lr', 'wd', 'b1', 'b2', 'eps')]
+    + [(k, ctypes.c_double) for k in ('max_norm', 'growth_factor', 'backoff_factor')]
+    + [(k, _I32) for k in ('growth_interval', 'scale_mode', 'skip_nonfinite', 'n_groups')]))
 FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
@@ -474,6 +478,11 @@ _SIGNATURES = {
     'sst_deform_conv_bwd_workspace_bytes': (c_i64, [c_ptr]),
     'sst_deform_conv_fwd_f32': (c_i32, [c_ptr] * 6),
     'sst_deform_conv_bwd_f32': (c_i32, [c_ptr] * 10),
+    'sst_optim_chunk_elems': (c_i32, []),
+    'sst_optim_max_groups': (c_i32, []),
+    'sst_optim_record_bytes': (c_i32, []),
+    'sst_optim_workspace_bytes': (c_i64, [c_i64]),
+    'sst_optim_step_f32': (c_i32, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
