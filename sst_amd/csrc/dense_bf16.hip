@@ -18,52 +18,16 @@
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
+#include "gelu.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short bf16_t;
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (RNE); compiler-visible
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)(pack2(v, 0.f) & 0xffffu); }
-__device__ __forceinline__ float lo_f(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ f32x4 mma32(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, far below the bf16 resolution of every consumer): one
-// reciprocal, one exponential and five FMAs instead of the ~40 instructions of the library's erff.
-// e = exp(-z^2) is returned too: the GELU derivative needs exp(-x^2 / 2) = e at z = x / sqrt(2).
-__device__ __forceinline__ float erf_as(float z, float& e) {
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.f));
-  e = __expf(-az * az);
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  return copysignf(fmaf(-poly, e, 1.f), z);
-}
-__device__ __forceinline__ float gelu_f(float x) {
-  float e;
-  return 0.5f * x * (1.f + erf_as(x * 0.70710678118654752f, e));
-}
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  float e;
-  const float phi = 0.5f * (1.f + erf_as(x * 0.70710678118654752f, e));
-  return fmaf(x * 0.3989422804014327f, e, phi);
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // Y = epi(X W^T + b)
 // ------------------------------------------------------------------------------------------------------------------
-enum { kEpiBias = 0, kEpiGelu = 1, kEpiRelu = 2, kEpiMulGeluGrad = 3, kEpiMulReluGrad = 4, kEpiAdd = 5, kEpiAddLN = 6 };
-
 // kEpiAddLN (N = 128): y = LayerNorm(x W^T + bias + residual) - `norm(src + src2)` of sst_basic_block_v2.py:113-118 in the
 // epilogue of the projection that produces src2 (out_proj / linear2).  A row's 128 columns sit in the four lanes (g = 0..3)
 // of its MFMA column, 32 values each: two shuffle reductions give the statistics.  Also written: the sum (bf16, for the
@@ -77,13 +41,6 @@ struct ln_epi {
   const int32_t* pos_idx;
   bf16_t* yp;
 };
-
-// LDS image of W: row rho = 16 T + i holds W[n(T, i)][0..K), n(T, i) = 32 (T >> 1) + 8 (i >> 2) + 4 (T & 1) + (i & 3):
-// tile pair (2 tp, 2 tp + 1) then leaves lane (g, c) with columns 32 tp + 8 g .. + 7 of row c.
-__device__ __forceinline__ int w_lds_row(int n) {
-  const int tp = n >> 5, within = n & 31;
-  return 16 * (2 * tp + ((within >> 2) & 1)) + ((within >> 3) << 2) + (within & 3);
-}
 
 template <int K, int N, int EPI, int NTH>
 __global__ __launch_bounds__(NTH, (NTH == 512 ? 2 : (K * N <= 128 * 128 ? 3 : 2))) void tall_linear_bf16_k(const bf16_t* __restrict__ X, int64_t ldx,

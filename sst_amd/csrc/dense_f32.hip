@@ -18,29 +18,10 @@
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
+#include "gelu.h"
+#include "mfma_tile.h"   // f32x4 and w_lds_row: the fp32 products leave a lane with the same 8 consecutive columns
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float erf_as(float z, float& e) {  // Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.f));
-  e = __expf(-az * az);
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  return copysignf(fmaf(-poly, e, 1.f), z);
-}
-__device__ __forceinline__ float gelu_f(float x) {
-  float e;
-  return 0.5f * x * (1.f + erf_as(x * 0.70710678118654752f, e));
-}
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  float e;
-  const float phi = 0.5f * (1.f + erf_as(x * 0.70710678118654752f, e));
-  return fmaf(x * 0.3989422804014327f, e, phi);
-}
-
-enum { kEpiBias = 0, kEpiGelu = 1, kEpiRelu = 2, kEpiMulGeluGrad = 3, kEpiMulReluGrad = 4, kEpiAdd = 5, kEpiAddLN = 6 };
 
 // kEpiAddLN (N = 128, 8-wave kernel): y = LayerNorm(x W^T + bias + residual) - `norm(src + src2)` of
 // sst_basic_block_v2.py:113-118 in the epilogue of the projection that produces src2.  A row's 128 columns sit in the four
@@ -55,11 +36,6 @@ struct ln_epi {
   const int32_t* pos_idx;
   float* yp;
 };
-
-__device__ __forceinline__ int w_lds_row(int n) {  // see csrc/dense_bf16.hip
-  const int tp = n >> 5, within = n & 31;
-  return 16 * (2 * tp + ((within >> 2) & 1)) + ((within >> 3) << 2) + (within & 3);
-}
 
 // 128 output columns x one 32-row (TWO) / 16-row step: W fragments are read one group ahead of the MFMAs that consume
 // them; the scheduling barriers keep the compiler from sinking the LDS read next to its first use, where its latency

@@ -21,54 +21,10 @@
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
+#include "gelu.h"
+#include "mfma_tile.h"   // the two-way split8
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (RNE); compiler-visible
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ f32x4 mma32(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// 8 floats -> (hi pack, lo pack): hi = bf16(x), lo = bf16(x - hi)
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
-  hi[0] = pack2(a[0], a[1]);
-  hi[1] = pack2(a[2], a[3]);
-  hi[2] = pack2(b[0], b[1]);
-  hi[3] = pack2(b[2], b[3]);
-  lo[0] = pack2(a[0] - lo_f(hi[0]), a[1] - hi_f(hi[0]));
-  lo[1] = pack2(a[2] - lo_f(hi[1]), a[3] - hi_f(hi[1]));
-  lo[2] = pack2(b[0] - lo_f(hi[2]), b[1] - hi_f(hi[2]));
-  lo[3] = pack2(b[2] - lo_f(hi[3]), b[3] - hi_f(hi[3]));
-}
-
-__device__ __forceinline__ float erf_as(float z, float& e) {  // Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.f));
-  e = __expf(-az * az);
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  return copysignf(fmaf(-poly, e, 1.f), z);
-}
-__device__ __forceinline__ float gelu_f(float x) {
-  float e;
-  return 0.5f * x * (1.f + erf_as(x * 0.70710678118654752f, e));
-}
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  float e;
-  const float phi = 0.5f * (1.f + erf_as(x * 0.70710678118654752f, e));
-  return fmaf(x * 0.3989422804014327f, e, phi);
-}
-
-enum { kEpiBias = 0, kEpiGelu = 1, kEpiRelu = 2, kEpiMulGeluGrad = 3, kEpiMulReluGrad = 4, kEpiAdd = 5, kEpiAddLN = 6 };
 
 struct ln_epi {   // see csrc/dense_f32.hip
   const float* w;
@@ -79,11 +35,6 @@ struct ln_epi {   // see csrc/dense_f32.hip
   const int32_t* pos_idx;
   float* yp;
 };
-
-__device__ __forceinline__ int w_lds_row(int n) {  // see csrc/dense_bf16.hip
-  const int tp = n >> 5, within = n & 31;
-  return 16 * (2 * tp + ((within >> 2) & 1)) + ((within >> 3) << 2) + (within & 3);
-}
 
 template <int K, int N, int EPI>
 __global__ __launch_bounds__(512, 2) void tall_linear_f32x3_k(

@@ -30,62 +30,11 @@
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
+#include "gelu.h"
+#include "mfma_tile.h"   // the three-way split8
 #include "tile_io.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (RNE); compiler-visible
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ f32x4 mma32(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// two floats -> their three bf16 parts, packed pairwise: p0 = bf16(x), p1 = bf16(x - p0), p2 = bf16(x - p0 - p1) (exact)
-__device__ __forceinline__ void split2(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2) {
-  p0 = pack2(a, b);
-  const float ra = a - lo_f(p0), rb = b - hi_f(p0);
-  p1 = pack2(ra, rb);
-  p2 = pack2(ra - lo_f(p1), rb - hi_f(p1));
-}
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, u32x4& p0, u32x4& p1, u32x4& p2) {
-  unsigned q0[4], q1[4], q2[4];
-  split2(a[0], a[1], q0[0], q1[0], q2[0]);
-  split2(a[2], a[3], q0[1], q1[1], q2[1]);
-  split2(b[0], b[1], q0[2], q1[2], q2[2]);
-  split2(b[2], b[3], q0[3], q1[3], q2[3]);
-  p0 = (u32x4){q0[0], q0[1], q0[2], q0[3]};
-  p1 = (u32x4){q1[0], q1[1], q1[2], q1[3]};
-  p2 = (u32x4){q2[0], q2[1], q2[2], q2[3]};
-}
-
-__device__ __forceinline__ float erf_as(float z, float& e) {  // Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.f));
-  e = __expf(-az * az);
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  return copysignf(fmaf(-poly, e, 1.f), z);
-}
-__device__ __forceinline__ float gelu_f(float x) {
-  float e;
-  return 0.5f * x * (1.f + erf_as(x * 0.70710678118654752f, e));
-}
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  float e;
-  const float phi = 0.5f * (1.f + erf_as(x * 0.70710678118654752f, e));
-  return fmaf(x * 0.3989422804014327f, e, phi);
-}
-
-enum { kEpiBias = 0, kEpiGelu = 1, kEpiRelu = 2, kEpiMulGeluGrad = 3, kEpiMulReluGrad = 4, kEpiAdd = 5, kEpiAddLN = 6,
-       kEpiAddRows = 7 };   // kEpiAddRows: + aux_in[row_index[row]] (ln.pos_idx; negative -> row 0): the split-weight VFE layer
 
 struct ln_epi {   // see csrc/dense_f32.hip
   const float* w;
@@ -96,11 +45,6 @@ struct ln_epi {   // see csrc/dense_f32.hip
   const int32_t* pos_idx;
   float* yp;
 };
-
-__device__ __forceinline__ int w_lds_row(int n) {  // see csrc/dense_bf16.hip: a lane ends with 8 consecutive columns of a row
-  const int tp = n >> 5, within = n & 31;
-  return 16 * (2 * tp + ((within >> 2) & 1)) + ((within >> 3) << 2) + (within & 3);
-}
 
 // The bias image leaves LDS where the eight 2 KiB transposition blocks (csrc/tile_io.h) do not fit beside it: <384, 64> has
 // 3 x 64 x 384 x 2 = 147 456 B of images, 163 840 - 147 456 = 16 384 B free = exactly 8 x 2 048; its 256 B of bias are then held in

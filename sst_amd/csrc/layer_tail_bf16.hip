@@ -16,25 +16,11 @@
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
+#include "gelu.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short bf16_t;
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (RNE)
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ f32x4 mma32(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ u32x4 pack8(const f32x4& a, const f32x4& b) {
   return (u32x4){pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(b[0], b[1]), pack2(b[2], b[3])};
 }
@@ -42,40 +28,8 @@ __device__ __forceinline__ void unpack8(const u32x4& p, f32x4& a, f32x4& b) {
   a = (f32x4){lo_f(p[0]), hi_f(p[0]), lo_f(p[1]), hi_f(p[1])};
   b = (f32x4){lo_f(p[2]), hi_f(p[2]), lo_f(p[3]), hi_f(p[3])};
 }
-__device__ __forceinline__ float erf_as(float z, float& e) {  // Abramowitz & Stegun 7.1.26 (as csrc/dense_bf16.hip)
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.f));
-  e = __expf(-az * az);
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  return copysignf(fmaf(-poly, e, 1.f), z);
-}
-__device__ __forceinline__ float gelu_f(float x) {
-  float e;
-  return 0.5f * x * (1.f + erf_as(x * 0.70710678118654752f, e));
-}
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  float e;
-  const float phi = 0.5f * (1.f + erf_as(x * 0.70710678118654752f, e));
-  return fmaf(x * 0.3989422804014327f, e, phi);
-}
-__device__ __forceinline__ int w_lds_row(int n) {  // see csrc/dense_bf16.hip: a lane ends with 8 consecutive columns of a row
-  const int tp = n >> 5, within = n & 31;
-  return 16 * (2 * tp + ((within >> 2) & 1)) + ((within >> 3) << 2) + (within & 3);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row_sum16(float v) {   // sum over the 16 lanes of a DPP row, every lane gets the total
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  return dpp_add<0x140>(v);
-}
-__device__ __forceinline__ void barrier_drain() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int kC = 128, kFF = 256, kHC = 64, kNF = kFF / kHC;   // 4 feed-forward chunks of 64 hidden columns
-constexpr int kFrag = 1024;
 constexpr int kP1 = 4 * 4 * kFrag;      // first product of a chunk: 4 row tiles (64 hidden columns) x 4 k-steps (K = 128)
 constexpr int kP2 = 8 * 2 * kFrag;      // second product: 8 row tiles (128 outputs) x 2 k-steps (the chunk's 64 hidden columns)
 constexpr int kSlot = kP1 + kP2;        // 32 KiB = the out-projection's 8 row tiles x 4 k-steps as well
@@ -93,11 +47,6 @@ struct tail_weights {
   const float* w1;   // [256][128]
   const float* w2;   // [128][256]
 };
-
-// byte offset inside an image of the 16 bytes (row lr of the image, k8 .. k8 + 7), the image having `ks` k-steps per row tile
-__device__ __forceinline__ int frag_off(int lr, int k8, int ks) {
-  return ((lr >> 4) * ks + (k8 >> 5)) * kFrag + (16 * ((k8 >> 3) & 3) + (lr & 15)) * 16;
-}
 
 // packed[dir][phase][kSlot]: dir 0 forward (phase 0 = out-projection, 1 .. 4 = feed-forward chunks), dir 1 backward (0 .. 3 =
 // feed-forward chunks of the TRANSPOSED products, 4 = out-projection^T).  One workgroup per phase image, an item = 8 k of one row.
@@ -134,12 +83,6 @@ __global__ __launch_bounds__(512) void encoder_tail_pack_bf16_k(const pack_batch
     }
     *(u32x4*)(img + off) = (u32x4){pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
   }
-}
-
-__device__ __forceinline__ void dma_pieces(const unsigned char* __restrict__ src, unsigned char* dst, int pieces, int wave, int lane) {
-  for (int i = wave; i < pieces; i += kWaves)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024 + lane * 16),
-                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
 }
 
 // ---- global memory <-> fragment layout through a wave-private 1 KiB LDS block (see csrc/layer_tail_x6.hip) -----------------
@@ -239,8 +182,8 @@ __global__ __launch_bounds__(kNTH, 4) void encoder_tail_fwd_bf16_k(const tail_fw
   const int64_t row = valid ? r0 + c : P.m - 1;
   const tile_io io = make_tile_io(lds + 2 * kSlot + kParF * 4 + wave * kScr, lane, r0, P.m);
   const unsigned char* packed = P.packed;
-  dma_pieces(packed, lds, kSlot / 1024, wave, lane);                    // out-projection -> slot 0
-  dma_pieces(packed + kSlot, lds + kSlot, kSlot / 1024, wave, lane);    // feed-forward chunk 0 -> slot 1
+  dma_pieces<kWaves>(packed, lds, kSlot / 1024, wave, lane);                    // out-projection -> slot 0
+  dma_pieces<kWaves>(packed + kSlot, lds + kSlot, kSlot / 1024, wave, lane);    // feed-forward chunk 0 -> slot 1
   u32x4 ob[4], xb[4];
   {
     u32x4 wo[4], wx[4];
@@ -296,7 +239,7 @@ __global__ __launch_bounds__(kNTH, 4) void encoder_tail_fwd_bf16_k(const tail_fw
     for (int T = 0; T < 8; ++T) acc[T] = z4;
   }
   barrier_drain();   // slot 0 is free
-  dma_pieces(packed + 2 * (size_t)kSlot, lds, kSlot / 1024, wave, lane);   // chunk 1 -> slot 0
+  dma_pieces<kWaves>(packed + 2 * (size_t)kSlot, lds, kSlot / 1024, wave, lane);   // chunk 1 -> slot 0
 #pragma unroll 1
   for (int j = 0; j < kNF; ++j) {
     const unsigned char* slot = lds + ((j + 1) & 1) * kSlot;
@@ -324,7 +267,7 @@ __global__ __launch_bounds__(kNTH, 4) void encoder_tail_fwd_bf16_k(const tail_fw
     mma_tiles<8, 2>(slot + kP1, lane_off, hb, acc);
     if (j + 1 < kNF) {
       barrier_drain();   // this chunk's slot is free; the next chunk's images (requested a phase ago) have landed
-      if (j + 2 < kNF) dma_pieces(packed + (size_t)(j + 3) * kSlot, lds + ((j + 1) & 1) * kSlot, kSlot / 1024, wave, lane);
+      if (j + 2 < kNF) dma_pieces<kWaves>(packed + (size_t)(j + 3) * kSlot, lds + ((j + 1) & 1) * kSlot, kSlot / 1024, wave, lane);
     }
   }
   // s2 = y1 + linear2 + b2; y2 = LN2(s2) (; y2p = y2 + positional rows of the next layer)
@@ -413,8 +356,8 @@ __global__ __launch_bounds__(kNTH, 4) void encoder_tail_bwd_bf16_k(const tail_bw
   const int64_t row = valid ? r0 + c : P.m - 1;
   const tile_io io = make_tile_io(lds + 2 * kSlot + kWaves * 2 * kC * 4 + wave * kScr, lane, r0, P.m);
   const unsigned char* packed = P.packed;
-  dma_pieces(packed, lds, kSlot / 1024, wave, lane);                    // chunk 0 -> slot 0
-  dma_pieces(packed + kSlot, lds + kSlot, kSlot / 1024, wave, lane);    // chunk 1 -> slot 1
+  dma_pieces<kWaves>(packed, lds, kSlot / 1024, wave, lane);                    // chunk 0 -> slot 0
+  dma_pieces<kWaves>(packed + kSlot, lds + kSlot, kSlot / 1024, wave, lane);    // chunk 1 -> slot 1
   f32x4 d[4][2], sv[4][2];
   {
     u32x4 wd[4], we[4], ws[4];
@@ -491,7 +434,7 @@ __global__ __launch_bounds__(kNTH, 4) void encoder_tail_bwd_bf16_k(const tail_bw
     }
     mma_tiles<8, 2>(slot + kP1, lane_off, hb, acc);
     barrier_drain();   // this chunk's slot is free; the next phase's images (requested a phase ago) have landed
-    if (j + 2 < kPhases) dma_pieces(packed + (size_t)(j + 2) * kSlot, lds + (j & 1) * kSlot, kSlot / 1024, wave, lane);
+    if (j + 2 < kPhases) dma_pieces<kWaves>(packed + (size_t)(j + 2) * kSlot, lds + (j & 1) * kSlot, kSlot / 1024, wave, lane);
   }
   // d(y1) = ds2 + dpre W1; norm1 backward -> ds1 (= d(x) of the residual, = d(out-projection output))
   f32x4 dd[4][2], xs[4][2];

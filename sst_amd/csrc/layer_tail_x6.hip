@@ -24,6 +24,8 @@
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
+#include "gelu.h"
+#include "mfma_tile.h"
 
 #ifndef SST_NT_OUT
 #define SST_NT_OUT false
@@ -34,41 +36,12 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (RNE)
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ f32x4 mma32(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// two floats -> their three bf16 parts, packed pairwise (exact: see csrc/dense_f32x6.hip)
-__device__ __forceinline__ void split2(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2) {
-  p0 = pack2(a, b);
-  const float ra = a - lo_f(p0), rb = b - hi_f(p0);
-  p1 = pack2(ra, rb);
-  p2 = pack2(ra - lo_f(p1), rb - hi_f(p1));
-}
 struct img3 {   // the three parts of 8 consecutive k of one token / one weight row
   u32x4 p0, p1, p2;
 };
-__device__ __forceinline__ img3 split8(const f32x4& a, const f32x4& b) {
-  unsigned q0[4], q1[4], q2[4];
-  split2(a[0], a[1], q0[0], q1[0], q2[0]);
-  split2(a[2], a[3], q0[1], q1[1], q2[1]);
-  split2(b[0], b[1], q0[2], q1[2], q2[2]);
-  split2(b[2], b[3], q0[3], q1[3], q2[3]);
+__device__ __forceinline__ img3 split8(const f32x4& a, const f32x4& b) {   // the exact three-way split of csrc/mfma_tile.h
   img3 r;
-  r.p0 = (u32x4){q0[0], q0[1], q0[2], q0[3]};
-  r.p1 = (u32x4){q1[0], q1[1], q1[2], q1[3]};
-  r.p2 = (u32x4){q2[0], q2[1], q2[2], q2[3]};
+  split8(a, b, r.p0, r.p1, r.p2);
   return r;
 }
 // the fp32 values back from their parts: (p2 + p1) + p0, both additions exact (p1 + p2 = x - p0 was formed exactly)
@@ -82,48 +55,10 @@ __device__ __forceinline__ void join8(const img3& v, f32x4& a, f32x4& b) {
   }
 }
 
-__device__ __forceinline__ float erf_as(float z, float& e) {  // Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7 (as dense_f32x6.hip)
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.f));
-  e = __expf(-az * az);
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-  return copysignf(fmaf(-poly, e, 1.f), z);
-}
-__device__ __forceinline__ float gelu_f(float x) {
-  float e;
-  return 0.5f * x * (1.f + erf_as(x * 0.70710678118654752f, e));
-}
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  float e;
-  const float phi = 0.5f * (1.f + erf_as(x * 0.70710678118654752f, e));
-  return fmaf(x * 0.3989422804014327f, e, phi);
-}
-
-__device__ __forceinline__ int w_lds_row(int n) {  // see csrc/dense_bf16.hip: a lane ends with 8 consecutive columns of a row
-  const int tp = n >> 5, within = n & 31;
-  return 16 * (2 * tp + ((within >> 2) & 1)) + ((within >> 3) << 2) + (within & 3);
-}
-
-// sum over the 16 lanes of a DPP row (the 16 tokens of a tile held by the lanes of one k group), every lane gets the total:
-// quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror - four v_add_f32 with a DPP operand, no LDS crossbar
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row_sum16(float v) {
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  return dpp_add<0x140>(v);
-}
-
 constexpr int kC = 128, kFF = 256, kHC = 32, kNF = kFF / kHC;   // 8 feed-forward chunks of 32 hidden columns
-// LDS images are FRAGMENT-contiguous: the 16 rows x 32 k (bf16) an MFMA A operand covers are one 1 KiB block in lane order
-// (lane (c, g) = row c, k 8 g .. 8 g + 7 at byte 16 * (16 g + c)), a fragment read is base + 16 * lane.  ds_read_b128 is served in
-// four groups of 16 NON-contiguous lanes ({0-3, 12-15, 20-27}, ... - MI355X_MICROARCH.md, LDS): a row-major image with a padded
-// row stride (K * 2 + 16 bytes, csrc/dense_f32x6.hip) puts two lanes of every group on the same banks - SQ_LDS_BANK_CONFLICT was
-// 42 % of SQ_LDS_IDX_ACTIVE; lane order has every group cover all 64 banks exactly once, and needs no padding.
-constexpr int kFrag = 1024;
+// LDS images are FRAGMENT-contiguous (kFrag, frag_off of csrc/mfma_tile.h).  ds_read_b128 is served in four groups of 16
+// NON-contiguous lanes ({0-3, 12-15, 20-27}, ... - MI355X_MICROARCH.md, LDS): a row-major image with a padded row stride (K * 2 +
+// 16 bytes) puts two lanes of every group on the same banks - SQ_LDS_BANK_CONFLICT was 42 % of SQ_LDS_IDX_ACTIVE.
 constexpr int kI1 = 2 * 4 * kFrag;      // a chunk's first product: 2 row tiles (32 hidden columns) x 4 k-steps (K = 128)
 constexpr int kI2 = 8 * 1 * kFrag;      // ... second product: 8 row tiles (128 outputs) x 1 k-step (the chunk's 32 hidden columns)
 constexpr int kIA = 8 * 2 * kFrag;      // an out-projection k-half: 8 row tiles x 2 k-steps
@@ -208,11 +143,6 @@ __device__ __forceinline__ void stage_load(const tail_weights W, int chunk, int 
   }
 }
 
-// byte offset inside an image of the 16 bytes (row lr of the image, k8 .. k8 + 7), the image having `ks` k-steps per row tile
-__device__ __forceinline__ int frag_off(int lr, int k8, int ks) {
-  return ((lr >> 4) * ks + (k8 >> 5)) * kFrag + (16 * ((k8 >> 3) & 3) + (lr & 15)) * 16;
-}
-
 __device__ __forceinline__ void store_images(unsigned char* base, int image_bytes, int off, const float* v) {
   const f32x4 a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
   const img3 s = split8(a, b);
@@ -265,22 +195,10 @@ __global__ __launch_bounds__(512) void encoder_tail_pack_k(const pack_batch B) {
   for (int i = threadIdx.x; i < kSlot / 16; i += 512) *(u32x4*)(dst + 16 * i) = *(const u32x4*)(lds + 16 * i);   // pads: whatever
 }
 
-// LDS-DMA of `pieces` KiB from src to the LDS offset dst (both 1 KiB pieces apart), the workgroup's waves taking pieces in turn.
-// Completion: the issuing wave's vmcnt, then a barrier (every caller below drains with __syncthreads()).
-__device__ __forceinline__ void dma_pieces(const unsigned char* __restrict__ src, unsigned char* dst, int pieces, int wave, int lane) {
-  for (int i = wave; i < pieces; i += kWaves)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024 + lane * 16),
-                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
-}
-
 // barrier that does NOT drain the vector-memory counter (stores / DMA stay in flight across it): the LDS reads of the phase it
 // ends are retired (lgkmcnt(0)), nothing else is waited for.  Only where no DMA has to have landed by this point.
+// (THE barrier of the chunk choreography is barrier_drain of csrc/mfma_tile.h.)
 __device__ __forceinline__ void barrier_lds_only() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// THE barrier of the chunk choreography: every vector-memory operation of this wave - its LDS-DMA pieces among them - and every
-// LDS operation has completed, then the workgroup meets.  Written out: __syncthreads() leaves the vmcnt wait to the compiler's
-// view of which LDS-DMA may alias which ds_read, and a missing one shows as rare wrong tiles in workgroups that start late
-// (found by running the kernel twice on the same input: 2 % of the s2 rows differed).
-__device__ __forceinline__ void barrier_drain() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- global memory <-> the MFMA fragment layout, through a wave-private LDS block ---------------------------------------------
 // In the fragment layout lane (c, g) holds 32 bytes of token c: consecutive lanes are consecutive ROWS, so a dwordx4 access of a
@@ -492,7 +410,7 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
   const tile_io io = make_tile_io(lds + kArea + kParF * 4 + wave * kScr, lane, r0, P.m);
   const unsigned char* packed = P.packed;
   unsigned char* const part2 = lds + kPart1;
-  dma_pieces(packed, lds, 3 * kIA / 1024, wave, lane);   // out-projection half 0
+  dma_pieces<kWaves>(packed, lds, 3 * kIA / 1024, wave, lane);   // out-projection half 0
   // the wave's o tile (B operand of the out-projection) and x tile (the residual: k-step s <-> columns 32 s ..)
   f32x4 ob[4][2], xr[4][2];
   {
@@ -531,11 +449,11 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
   barrier_drain();
   mma_half<0>(lds, lane_offA, ob, acc);
   barrier_drain();
-  dma_pieces(packed + kSlot, lds, 3 * kIA / 1024, wave, lane);
+  dma_pieces<kWaves>(packed + kSlot, lds, 3 * kIA / 1024, wave, lane);
   barrier_drain();
   mma_half<1>(lds, lane_offA, ob, acc);
   barrier_drain();
-  dma_pieces(packed + 2 * kSlot, lds, kSlot / 1024, wave, lane);   // feed-forward chunk 0, both parts (landed at the next barrier)
+  dma_pieces<kWaves>(packed + 2 * kSlot, lds, kSlot / 1024, wave, lane);   // feed-forward chunk 0, both parts (landed at the next barrier)
   {
     // s1 = out-proj + b_o + x; y1 = LN1(s1)
     f32x4 v[4][2];
@@ -581,11 +499,11 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
     }
     const img3 hs = split8(h0, h1);
     barrier_drain();   // part 1 is free; this chunk's part 2 has landed; the previous chunk's stores are acknowledged
-    if (j + 1 < kNF) dma_pieces(packed + (size_t)(j + 3) * kSlot, lds, kPart1 / 1024, wave, lane);
+    if (j + 1 < kNF) dma_pieces<kWaves>(packed + (size_t)(j + 3) * kSlot, lds, kPart1 / 1024, wave, lane);
     mma_second(part2, lane_off2, hs, acc);
     sp0 = p0, sp1 = p1, sh0 = h0, sh1 = h1;
     barrier_drain();   // part 2 is free, the next chunk's part 1 has landed (nothing else is in flight)
-    if (j + 1 < kNF) dma_pieces(packed + (size_t)(j + 3) * kSlot + kPart1, part2, kPart2 / 1024, wave, lane);
+    if (j + 1 < kNF) dma_pieces<kWaves>(packed + (size_t)(j + 3) * kSlot + kPart1, part2, kPart2 / 1024, wave, lane);
   }
   store32<true>(io, P.pre, kFF, kHC * (kNF - 1), sp0, sp1);
   store32<true>(io, P.h, kFF, kHC * (kNF - 1), sh0, sh1);
@@ -676,7 +594,7 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_
   const tile_io io = make_tile_io(lds + kArea + 2 * kC * 4 + kWaves * 2 * kC * 4 + wave * kScr, lane, r0, P.m);
   const unsigned char* packed = P.packed;
   unsigned char* const part2 = lds + kPart1;
-  dma_pieces(packed, lds, kSlot / 1024, wave, lane);   // feed-forward chunk 0, both parts: lands behind the first LayerNorm backward
+  dma_pieces<kWaves>(packed, lds, kSlot / 1024, wave, lane);   // feed-forward chunk 0, both parts: lands behind the first LayerNorm backward
   f32x4 d[4][2], sv[4][2];
   {
     f32x4 wd[4][2], we[4][2];
@@ -737,14 +655,14 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_
     }
     const img3 hs = split8(p0, p1);
     barrier_drain();   // part 1 is free (and this chunk's part 2 has landed)
-    if (j + 1 < kNF) dma_pieces(packed + (size_t)(j + 1) * kSlot, lds, kPart1 / 1024, wave, lane);
+    if (j + 1 < kNF) dma_pieces<kWaves>(packed + (size_t)(j + 1) * kSlot, lds, kPart1 / 1024, wave, lane);
     mma_second(part2, lane_off2, hs, acc);
     sd0 = p0, sd1 = p1;
     barrier_drain();   // part 2 is free, the next chunk's part 1 has landed
     if (j + 1 < kNF)
-      dma_pieces(packed + (size_t)(j + 1) * kSlot + kPart1, part2, kPart2 / 1024, wave, lane);
+      dma_pieces<kWaves>(packed + (size_t)(j + 1) * kSlot + kPart1, part2, kPart2 / 1024, wave, lane);
     else
-      dma_pieces(packed + (size_t)kNF * kSlot, lds, 3 * kIA / 1024, wave, lane);   // out-projection half 0: lands behind norm1's backward
+      dma_pieces<kWaves>(packed + (size_t)kNF * kSlot, lds, 3 * kIA / 1024, wave, lane);   // out-projection half 0: lands behind norm1's backward
   };
   // norm2's parameter-gradient partials of this workgroup leave now: the reduction area is used again by norm1's
   barrier_drain();   // chunk 0's images have landed; all waves' column sums are in LDS
@@ -796,7 +714,7 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_
     barrier_drain();   // out-projection half 0 has landed
     mma_half<0>(lds, lane_offA, xs1, acc);
     barrier_drain();
-    dma_pieces(packed + (size_t)(kNF + 1) * kSlot, lds, 3 * kIA / 1024, wave, lane);
+    dma_pieces<kWaves>(packed + (size_t)(kNF + 1) * kSlot, lds, 3 * kIA / 1024, wave, lane);
     barrier_drain();
     mma_half<1>(lds, lane_offA, xs1, acc);
   }

@@ -36,10 +36,9 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma_tile.h"   // split2 and mma32 of sp_wgrad_os_x6_k (the other kernels here run the fp32 instruction)
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Debug instrumentation (build with -DSST_OS_TIMING, see tools/conv_os_phases.py): per-wave phase times of sp_conv_os_k
 // in ticks of the constant 100 MHz clock.  Compiled out of the product library.
@@ -498,23 +497,6 @@ __global__ __launch_bounds__(256) void sp_wgrad_os_reduce_k(const float* __restr
 // G ^ f(r), f(r) = ((r >> 1) & 7) ^ ((r >> 3) & 7): the sixteen rows of a fragment read cover all 64 banks once, the sixteen
 // channel blocks of a write land two per 8-byte slot.  One buffer (48 KB, three workgroups per CU): the stage in registers
 // waits for a barrier behind the products of the stage in LDS.
-__device__ __forceinline__ unsigned wx6_pack2(float lo, float hi) {
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  const bf2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void wx6_split2(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2) {
-  p0 = wx6_pack2(a, b);
-  const float ra = a - __uint_as_float(p0 << 16), rb = b - __uint_as_float(p0 & 0xffff0000u);
-  p1 = wx6_pack2(ra, rb);
-  p2 = wx6_pack2(ra - __uint_as_float(p1 << 16), rb - __uint_as_float(p1 & 0xffff0000u));
-}
-typedef unsigned wx6_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned wx6_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 wx6_mma(wx6_u32x4 a, wx6_u32x4 b, f32x4 c) {
-  typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ int wx6_unit(int row, int G) { return (G ^ ((row >> 1) & 7) ^ ((row >> 3) & 7)) & 7; }
 
 __global__ __launch_bounds__(256) void sp_wgrad_os_x6_k(const float* __restrict__ x, int64_t ldx,
@@ -565,16 +547,16 @@ __global__ __launch_bounds__(256) void sp_wgrad_os_x6_k(const float* __restrict_
       const int row = 4 * ch4 + e;
       const int off = row * 128 + wx6_unit(row, pq >> 1) * 16 + (pq & 1) * 8;
       unsigned a0[2], a1[2], a2[2], b0[2], b1[2], b2[2];
-      wx6_split2(live[0] ? ra[0][e] : 0.f, live[1] ? ra[1][e] : 0.f, a0[0], a1[0], a2[0]);
-      wx6_split2(live[2] ? ra[2][e] : 0.f, live[3] ? ra[3][e] : 0.f, a0[1], a1[1], a2[1]);
-      wx6_split2(rb[0][e], rb[1][e], b0[0], b1[0], b2[0]);
-      wx6_split2(rb[2][e], rb[3][e], b0[1], b1[1], b2[1]);
-      *(wx6_u32x2*)(img[0] + off) = (wx6_u32x2){a0[0], a0[1]};
-      *(wx6_u32x2*)(img[1] + off) = (wx6_u32x2){a1[0], a1[1]};
-      *(wx6_u32x2*)(img[2] + off) = (wx6_u32x2){a2[0], a2[1]};
-      *(wx6_u32x2*)(img[3] + off) = (wx6_u32x2){b0[0], b0[1]};
-      *(wx6_u32x2*)(img[4] + off) = (wx6_u32x2){b1[0], b1[1]};
-      *(wx6_u32x2*)(img[5] + off) = (wx6_u32x2){b2[0], b2[1]};
+      split2(live[0] ? ra[0][e] : 0.f, live[1] ? ra[1][e] : 0.f, a0[0], a1[0], a2[0]);
+      split2(live[2] ? ra[2][e] : 0.f, live[3] ? ra[3][e] : 0.f, a0[1], a1[1], a2[1]);
+      split2(rb[0][e], rb[1][e], b0[0], b1[0], b2[0]);
+      split2(rb[2][e], rb[3][e], b0[1], b1[1], b2[1]);
+      *(u32x2*)(img[0] + off) = (u32x2){a0[0], a0[1]};
+      *(u32x2*)(img[1] + off) = (u32x2){a1[0], a1[1]};
+      *(u32x2*)(img[2] + off) = (u32x2){a2[0], a2[1]};
+      *(u32x2*)(img[3] + off) = (u32x2){b0[0], b0[1]};
+      *(u32x2*)(img[4] + off) = (u32x2){b1[0], b1[1]};
+      *(u32x2*)(img[5] + off) = (u32x2){b2[0], b2[1]};
     }
   };
   f32x4 acc[2][2], cor[2][2];   // leading product | the five corrections
@@ -594,42 +576,42 @@ __global__ __launch_bounds__(256) void sp_wgrad_os_x6_k(const float* __restrict_
     __builtin_amdgcn_sched_barrier(0);   // the loads are issued HERE, in front of the products that hide their latency
 #pragma unroll
     for (int ks = 0; ks < kWgStage / 32; ++ks) {
-      wx6_u32x4 af[2][3], bf[2][3];
+      u32x4 af[2][3], bf[2][3];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int ra_ = wi + 16 * h + l15, rb_ = wj + 16 * h + l15;
         const int oa = ra_ * 128 + wx6_unit(ra_, 4 * ks + g) * 16, ob = rb_ * 128 + wx6_unit(rb_, 4 * ks + g) * 16;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-          af[h][q] = *(const wx6_u32x4*)(img[q] + oa);
-          bf[h][q] = *(const wx6_u32x4*)(img[3 + q] + ob);
+          af[h][q] = *(const u32x4*)(img[q] + oa);
+          bf[h][q] = *(const u32x4*)(img[3 + q] + ob);
         }
       }
       // smallest products first (x2 d0, x0 d2, x1 d1 ~ 2^-16; x1 d0, x0 d1 ~ 2^-8), product by product over the four tiles
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) cor[a][b] = wx6_mma(af[a][2], bf[b][0], cor[a][b]);
+        for (int b = 0; b < 2; ++b) cor[a][b] = mma32(af[a][2], bf[b][0], cor[a][b]);
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) cor[a][b] = wx6_mma(af[a][0], bf[b][2], cor[a][b]);
+        for (int b = 0; b < 2; ++b) cor[a][b] = mma32(af[a][0], bf[b][2], cor[a][b]);
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) cor[a][b] = wx6_mma(af[a][1], bf[b][1], cor[a][b]);
+        for (int b = 0; b < 2; ++b) cor[a][b] = mma32(af[a][1], bf[b][1], cor[a][b]);
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) cor[a][b] = wx6_mma(af[a][1], bf[b][0], cor[a][b]);
+        for (int b = 0; b < 2; ++b) cor[a][b] = mma32(af[a][1], bf[b][0], cor[a][b]);
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) cor[a][b] = wx6_mma(af[a][0], bf[b][1], cor[a][b]);
+        for (int b = 0; b < 2; ++b) cor[a][b] = mma32(af[a][0], bf[b][1], cor[a][b]);
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = wx6_mma(af[a][0], bf[b][0], acc[a][b]);
+        for (int b = 0; b < 2; ++b) acc[a][b] = mma32(af[a][0], bf[b][0], acc[a][b]);
     }
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();                // every wave has read this stage's images

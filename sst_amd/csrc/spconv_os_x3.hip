@@ -17,38 +17,13 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma_tile.h"   // the two-way split8
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kX3MaxK = 32;    // kernel offsets the index image holds
 constexpr int kX3Chunk = 64;   // input channels per stage
 constexpr int kX3XcdChunk = 4;
-
-__device__ __forceinline__ unsigned x3_pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (round to nearest even)
-  const bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float x3_lo_f(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float x3_hi_f(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ f32x4 x3_mma(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// 8 consecutive fp32 values -> their bf16 heads and the bf16 of what the heads leave
-__device__ __forceinline__ void x3_split8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo) {
-  hi[0] = x3_pack2(a[0], a[1]);
-  hi[1] = x3_pack2(a[2], a[3]);
-  hi[2] = x3_pack2(b[0], b[1]);
-  hi[3] = x3_pack2(b[2], b[3]);
-  lo[0] = x3_pack2(a[0] - x3_lo_f(hi[0]), a[1] - x3_hi_f(hi[0]));
-  lo[1] = x3_pack2(a[2] - x3_lo_f(hi[1]), a[3] - x3_hi_f(hi[1]));
-  lo[2] = x3_pack2(b[0] - x3_lo_f(hi[2]), b[1] - x3_hi_f(hi[2]));
-  lo[3] = x3_pack2(b[2] - x3_lo_f(hi[3]), b[3] - x3_hi_f(hi[3]));
-}
 
 // Packed weights: slab (k, column group cg, channel chunk cc) = [2 ks][NCT ct][2 hi|lo][64 lanes][4 words of 2 bf16], with
 //   the 8 values of lane (l15, g) = W[k][c = 64 cc + 32 ks + 8 g + 0..7][n = 16 NCT cg + 16 ct + l15]   (0 outside cin x cout):
@@ -78,7 +53,7 @@ __global__ __launch_bounds__(256) void sp_x3_pack_w_k(const float* __restrict__ 
       if (c < cin && n < cout) v[t] = trans_w ? w[((int64_t)k * cout + n) * cin + c] : w[((int64_t)k * cin + c) * cout + n];
     }
     u32x4 hi, lo;
-    x3_split8((f32x4){v[0], v[1], v[2], v[3]}, (f32x4){v[4], v[5], v[6], v[7]}, hi, lo);
+    split8((f32x4){v[0], v[1], v[2], v[3]}, (f32x4){v[4], v[5], v[6], v[7]}, hi, lo);
     // slab base in words: ((k, cg, cc) * 2 * nct * 2 * 64 * 4); inside: [ks][ct][hi|lo][lane][4]
     unsigned* dst = wp + ((((int64_t)(k * n_cg + cg) * n_cc + cc) * 2 + ks) * nct + ct) * 2 * 256;
     *(u32x4*)(dst + lane * 4) = hi;
@@ -162,8 +137,8 @@ __global__ __launch_bounds__(256, NCT == 4 ? 4 : 2) void sp_conv_os_x3_k(
 #pragma unroll
       for (int u = 0; u < WREG; ++u) *(u32x4*)(&wbuf[buf][4 * (tid + 256 * u)]) = wr[u];
       const bool has = sn >= 0;     // rows without a partner contribute 0
-      x3_split8(has ? xn[0] : zero4, has ? xn[1] : zero4, xh[0], xl[0]);
-      x3_split8(has ? xn[2] : zero4, has ? xn[3] : zero4, xh[1], xl[1]);
+      split8(has ? xn[0] : zero4, has ? xn[1] : zero4, xh[0], xl[0]);
+      split8(has ? xn[2] : zero4, has ? xn[3] : zero4, xh[1], xl[1]);
     };
     auto next_live = [&](int k) {
       const unsigned rest = k < 32 ? (live >> k) : 0u;
@@ -195,9 +170,9 @@ __global__ __launch_bounds__(256, NCT == 4 ? 4 : 2) void sp_conv_os_x3_k(
           for (int ct = 0; ct < NCT; ++ct) {
             const u32x4 wh = *(const u32x4*)(wb + ((ks * NCT + ct) * 2 + 0) * 256);
             const u32x4 wl = *(const u32x4*)(wb + ((ks * NCT + ct) * 2 + 1) * 256);
-            acc[ct] = x3_mma(wh, xh[ks], acc[ct]);
-            acc[ct] = x3_mma(wh, xl[ks], acc[ct]);
-            acc[ct] = x3_mma(wl, xh[ks], acc[ct]);
+            acc[ct] = mma32(wh, xh[ks], acc[ct]);
+            acc[ct] = mma32(wh, xl[ks], acc[ct]);
+            acc[ct] = mma32(wl, xh[ks], acc[ct]);
           }
         }
       }

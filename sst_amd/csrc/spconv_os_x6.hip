@@ -17,44 +17,13 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma_tile.h"   // the three-way split8
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kX6MaxK = 32;    // kernel offsets the index image holds
 constexpr int kX6Chunk = 64;   // input channels per stage
 constexpr int kX6XcdChunk = 4;
-
-__device__ __forceinline__ unsigned x6_pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (round to nearest even)
-  const bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float x6_lo_f(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float x6_hi_f(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ f32x4 x6_mma(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// 8 consecutive fp32 values -> their three bf16 parts (p0 = bf16(x), p1 = bf16(x - p0), p2 = x - p0 - p1: exact)
-__device__ __forceinline__ void x6_split2(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2) {
-  p0 = x6_pack2(a, b);
-  const float ra = a - x6_lo_f(p0), rb = b - x6_hi_f(p0);
-  p1 = x6_pack2(ra, rb);
-  p2 = x6_pack2(ra - x6_lo_f(p1), rb - x6_hi_f(p1));
-}
-__device__ __forceinline__ void x6_split8(const f32x4& a, const f32x4& b, u32x4& p0, u32x4& p1, u32x4& p2) {
-  unsigned q0[4], q1[4], q2[4];
-  x6_split2(a[0], a[1], q0[0], q1[0], q2[0]);
-  x6_split2(a[2], a[3], q0[1], q1[1], q2[1]);
-  x6_split2(b[0], b[1], q0[2], q1[2], q2[2]);
-  x6_split2(b[2], b[3], q0[3], q1[3], q2[3]);
-  p0 = (u32x4){q0[0], q0[1], q0[2], q0[3]};
-  p1 = (u32x4){q1[0], q1[1], q1[2], q1[3]};
-  p2 = (u32x4){q2[0], q2[1], q2[2], q2[3]};
-}
 
 // Packed weights: slab (k, column group cg, channel chunk cc) = [2 ks][NCT ct][3 parts][64 lanes][4 words of 2 bf16], with
 //   the 8 values of lane (l15, g) = W[k][c = 64 cc + 32 ks + 8 g + 0..7][n = 16 NCT cg + 16 ct + l15]   (0 outside cin x cout):
@@ -84,7 +53,7 @@ __global__ __launch_bounds__(256) void sp_x6_pack_w_k(const float* __restrict__ 
       if (c < cin && n < cout) v[t] = trans_w ? w[((int64_t)k * cout + n) * cin + c] : w[((int64_t)k * cin + c) * cout + n];
     }
     u32x4 p0, p1, p2;
-    x6_split8((f32x4){v[0], v[1], v[2], v[3]}, (f32x4){v[4], v[5], v[6], v[7]}, p0, p1, p2);
+    split8((f32x4){v[0], v[1], v[2], v[3]}, (f32x4){v[4], v[5], v[6], v[7]}, p0, p1, p2);
     // slab base in words: ((k, cg, cc) * 2 * nct * 3 * 64 * 4); inside: [ks][ct][part][lane][4]
     unsigned* dst = wp + ((((int64_t)(k * n_cg + cg) * n_cc + cc) * 2 + ks) * nct + ct) * 3 * 256;
     *(u32x4*)(dst + lane * 4) = p0;
@@ -179,8 +148,8 @@ __global__ __launch_bounds__(256, NCT == 4 ? 2 : 1) void sp_conv_os_x6_k(
 #pragma unroll
       for (int u = 0; u < WREG; ++u) *(u32x4*)(&wbuf[buf][4 * (tid + 256 * u)]) = wr[u];
       const bool has = sn >= 0;     // rows without a partner contribute 0
-      x6_split8(has ? xn[0] : zero4, has ? xn[1] : zero4, x0[0], x1[0], x2[0]);
-      x6_split8(has ? xn[2] : zero4, has ? xn[3] : zero4, x0[1], x1[1], x2[1]);
+      split8(has ? xn[0] : zero4, has ? xn[1] : zero4, x0[0], x1[0], x2[0]);
+      split8(has ? xn[2] : zero4, has ? xn[3] : zero4, x0[1], x1[1], x2[1]);
     };
     auto next_live = [&](int k) {
       const unsigned rest = k < 32 ? (live >> k) : 0u;
@@ -214,12 +183,12 @@ __global__ __launch_bounds__(256, NCT == 4 ? 2 : 1) void sp_conv_os_x6_k(
             const u32x4 w1 = *(const u32x4*)(wb + ((ks * NCT + ct) * 3 + 1) * 256);
             const u32x4 w2 = *(const u32x4*)(wb + ((ks * NCT + ct) * 3 + 2) * 256);
             // corrections, smallest first: (0,2) (2,0) (1,1) ~ 2^-16, (0,1) (1,0) ~ 2^-8; then the leading product
-            acl[ct] = x6_mma(w0, x2[ks], acl[ct]);
-            acl[ct] = x6_mma(w2, x0[ks], acl[ct]);
-            acl[ct] = x6_mma(w1, x1[ks], acl[ct]);
-            acl[ct] = x6_mma(w0, x1[ks], acl[ct]);
-            acl[ct] = x6_mma(w1, x0[ks], acl[ct]);
-            acc[ct] = x6_mma(w0, x0[ks], acc[ct]);
+            acl[ct] = mma32(w0, x2[ks], acl[ct]);
+            acl[ct] = mma32(w2, x0[ks], acl[ct]);
+            acl[ct] = mma32(w1, x1[ks], acl[ct]);
+            acl[ct] = mma32(w0, x1[ks], acl[ct]);
+            acl[ct] = mma32(w1, x0[ks], acl[ct]);
+            acc[ct] = mma32(w0, x0[ks], acc[ct]);
           }
         }
       }

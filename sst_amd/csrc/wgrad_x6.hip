@@ -30,31 +30,9 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "mfma_tile.h"   // split2
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (RNE); compiler-visible
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float hi_f(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ f32x4 mma32(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void split2(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2) {
-  p0 = pack2(a, b);
-  const float ra = a - lo_f(p0), rb = b - hi_f(p0);
-  p1 = pack2(ra, rb);
-  p2 = pack2(ra - lo_f(p1), rb - hi_f(p1));
-}
 
 // a 64-bit value that is the same in all lanes, handed to the scalar side (addresses and loop bounds of the lean loop)
 __device__ __forceinline__ int64_t uniform64(int64_t v) {
