@@ -1987,6 +1987,101 @@ int64_t sst_optim_workspace_bytes(int64_t n_tensors);
 int sst_optim_step_f32(const sst_optim_tensor* d_tensors, int64_t n_tensors, const sst_optim_chunk* d_chunks, int64_t n_chunks,
                        const sst_optim_hyper* hyper, float* d_steps, void* d_record, void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The CTRL tracklet family (csrc/tracklet.hip): TrackletRoIHead's training targets and the input rows of its box head.
+ * fp32 data, int64 timestamps and offsets, no float atomics, no host read-back, bit-reproducible.
+ *
+ * sst_tracklet_targets_f32 - one launch for the whole batch, one workgroup (sst_tracklet_targets_block() threads) per tracklet.
+ *   Replaces tracklet_roi_head.py:333-347 (_select_one2one_candidates: one aligned_iou_3d launch, one .sum() and one host
+ *   tensor per candidate, torch.argmax(...).item()), :287-331 (_assign_and_sample per tracklet), tracklet_assigner.py:14-55
+ *   (TrackletAssigner.assign: Python timestamp walks, overlaps[i].item() per box), lidar_tracklet.py:278-299 (self_ious /
+ *   intersection_ious), mmdet's PseudoSampler and fsd_bbox_head.py:343-543 (get_targets / _get_target_single /
+ *   get_multi_class_soft_label per tracklet).  Every output size follows from the tracklet lengths the host knows.
+ *   Inputs: boxes [n_rows, 7] tracklet-major in frame order, ts int64 [n_rows] ascending within a tracklet, scores [n_rows],
+ *   trk_offsets int64 [n_tracklets + 1] (rows), cand_boxes [n_cand_rows, 7], cand_ts int64 [n_cand_rows] ascending within a
+ *   candidate, cand_offsets int64 [n_cands + 1] (candidate rows), trk_cand_offsets int64 [n_tracklets + 1] (candidates of a
+ *   tracklet), trk_class int64 [n_tracklets] in [0, num_classes).  Offsets are clamped to their arrays.
+ *   Candidate choice: per candidate the number of shared timestamps whose aligned 3-D IoU is > candidate_thresh (strict); the
+ *   chosen one is the FIRST with the maximal count - what torch.argmax returns on the reference's int64 host tensor (checked
+ *   on the CPU: torch.argmax(torch.tensor([2, 5, 5, 1])) == 1, and tests/test_tracklet_host.py pins it); chosen[t] = its index
+ *   into the candidates, -1 for a tracklet without candidates (the reference's empty ground-truth tracklet).
+ *   Per row in frame order: matched int32 (index of the chosen candidate's box with the same timestamp within that candidate,
+ *   -1 if none = get_index_from_ts), overlaps (the IoU with it, 0 if none = self_ious), assigned_gt_inds int64 (matched + 1;
+ *   with object_centric only where IoU > iou_thr, else 0).  The IoU is the device function sst_boxes_overlap_aligned_f32 uses
+ *   (bev_clip.h) x the height overlap over the union volume: bit-equal to aligned_iou_3d built on that entry point.
+ *   Per row in PseudoSampler's order (positives in frame order, then negatives in frame order; ranks by wave ballots and a scan
+ *   over the waves, no atomics), rows of tracklet t at trk_offsets[t] ..: the layout of sst_roi_sample_targets_f32 without
+ *   padding - rois [n_rows, 8] = (t, box), src int32 (input row), gt_index int32 (row of cand_boxes, -1 off the positives),
+ *   labels int64 (the tracklet's class, -1 off the positives), iou_out, soft_label (cls_pos_thr / cls_neg_thr of the class; 0
+ *   on negatives), reg_mask uint8, targets [n_rows, 7] (_get_target_single; 0 off the positives) - and frame_inds int64
+ *   (bboxes_frame_inds), scores_out, pos_gt_bboxes [n_rows, 7] (the matched box, 0 off the positives); counts int32
+ *   [n_tracklets, 2] = (positives, negatives).  Every element is written.
+ *
+ * sst_tracklet_rows_fwd_f32 / _bwd_f32 - tracklet_roi_head.py:247-258, the gathers and cats in front of the box head:
+ *   out[i] = (feats[p_i, 0 : feat_cols] | is_cur_frame_i if combined | roi_scores[r_i] if with_roi_scores), xyz_out[i] =
+ *   xyz[p_i, 0 : xyz_cols] (optional), p = pts_inds int64 [m], r = roi_inds int64 [m], is_cur_frame = pts_frame_inds[p] ==
+ *   roi_frame_inds[r].  A negative index counts from the end as Python's does (-1, the pool's fake row, reads the last row);
+ *   an index outside the array reads zeros.  feat_cols need not be a multiple of 4: the 16-byte-aligned part of a source row is
+ *   read as float4; the rows of a workgroup are staged in LDS and leave as one contiguous span, consecutive lanes on consecutive
+ *   floats.  Backward (replaces autograd's index_put): d_feats[p] = the sum of d_out[row, 0 : feat_cols] over the output rows of
+ *   p in ascending row order.  sst_tracklet_rows_keys_i64 writes key[i] = p_i * m + i (INT64_MAX for a row that names no point);
+ *   the caller sorts the keys (any sort: they are distinct); sst_tracklet_rows_bwd_f32 zeroes d_feats [n_points, feat_cols] (one
+ *   memset) and walks every run of the sorted keys once.  No float atomic; two runs are bit-equal.
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer or a negative size, SST_ERR_UNSUPPORTED for num_classes
+ * outside 1..SST_ROI_MAX_CLASSES or sizes above 2^31 - 1.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sst_tracklet_targets_args {
+  const float* boxes;
+  const int64_t* ts;
+  const float* scores;
+  const int64_t* trk_offsets;
+  const float* cand_boxes;
+  const int64_t* cand_ts;
+  const int64_t* cand_offsets;
+  const int64_t* trk_cand_offsets;
+  const int64_t* trk_class;
+  int32_t* chosen;
+  int32_t* counts;
+  int32_t* matched;
+  float* overlaps;
+  int64_t* assigned_gt_inds;
+  float* rois;
+  int32_t* src;
+  int64_t* frame_inds;
+  int32_t* gt_index;
+  int64_t* labels;
+  float* iou_out;
+  float* scores_out;
+  float* soft_label;
+  uint8_t* reg_mask;
+  float* targets;
+  float* pos_gt_bboxes;
+  int64_t n_rows, n_cand_rows, n_cands, n_tracklets;
+  int32_t num_classes, object_centric;
+  float candidate_thresh, iou_thr;
+  double cls_pos_thr[SST_ROI_MAX_CLASSES], cls_neg_thr[SST_ROI_MAX_CLASSES];
+} sst_tracklet_targets_args;
+typedef struct sst_tracklet_rows_args {
+  const float* feats;
+  const float* xyz;
+  const int64_t* pts_frame_inds;
+  const int64_t* pts_inds;
+  const int64_t* roi_inds;
+  const int64_t* roi_frame_inds;
+  const float* roi_scores;
+  float* out;
+  float* xyz_out;
+  int64_t m, n_points, n_rois, ld_feats, ld_xyz;
+  int32_t feat_cols, xyz_cols, combined, with_roi_scores;
+} sst_tracklet_rows_args;
+/* threads of a workgroup of the targets kernel (replaces nothing: the launch constant the tests size their cases by) */
+int sst_tracklet_targets_block(void);
+int sst_tracklet_targets_f32(const sst_tracklet_targets_args* args, void* stream);
+int sst_tracklet_rows_fwd_f32(const sst_tracklet_rows_args* args, void* stream);
+int sst_tracklet_rows_keys_i64(const int64_t* d_pts_inds, int64_t m, int64_t n_points, int64_t* d_keys, void* stream);
+int sst_tracklet_rows_bwd_f32(const float* d_out_grad, int64_t m, int64_t ld_out, int feat_cols, const int64_t* d_sorted_keys,
+                              int64_t n_points, float* d_feats_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

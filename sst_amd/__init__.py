@@ -65,10 +65,17 @@ from .deform_conv import (DeformConv2d, DeformConv2dPack, deform_conv2d, deform_
 from . import optim  # noqa: F401
 from .optim import (CyclicLr, CyclicMomentum, FusedAdamW, TrainingUpdate, build_optimizer,  # noqa: F401
                     build_training_update)
+from . import tracklet  # noqa: F401
+from .tracklet import LiDARTracklet, TrackletAssigner, aligned_iou_3d, tracklet_rows, tracklet_targets  # noqa: F401
+from . import tracklet_detector  # noqa: F401
+from .tracklet_detector import (TimestampEncoder, TrackletDetector, TrackletPointRoIExtractor, TrackletRoIHead,  # noqa: F401
+                                TrackletSegmentor, get_bboxes_from_tracklet)
 
 __version__ = '0.1.0'
 
 __all__ = [
+    'tracklet_detector', 'TimestampEncoder', 'TrackletDetector', 'TrackletPointRoIExtractor', 'TrackletRoIHead', 'TrackletSegmentor',
+    'get_bboxes_from_tracklet', 'tracklet', 'LiDARTracklet', 'TrackletAssigner', 'aligned_iou_3d', 'tracklet_rows', 'tracklet_targets',
     'VirtualVoxelExtractor', 'detectors', 'DynamicVoxelNet', 'DynamicCenterPoint', 'install_fused_extract_feat', 'DETECTORS', 'HEADS', 'NECKS', 'FSD', 'FSDV2', 'SingleStageFSD', 'SingleStageFSDV2',
     'VoteSegHead', 'VoteSegmentor', 'Voxel2PointScatterNeck', 'build_detector', 'build_head', 'build_model', 'build_neck',
     'Voxelization', 'voxelization', 'DynamicScatter', 'dynamic_scatter', 'dynamic_voxelize',

@@ -116,6 +116,20 @@ OptimHyper = _struct('OptimHyper', 'sst_optim_hyper of include/sst_amd.h', (
     [(k, ctypes.c_double * 8) for k in ('lr', 'wd', 'b1', 'b2', 'eps')]
     + [(k, ctypes.c_double) for k in ('max_norm', 'growth_factor', 'backoff_factor')]
     + [(k, _I32) for k in ('growth_interval', 'scale_mode', 'skip_nonfinite', 'n_groups')]))
+TrackletTargetsArgs = _struct('TrackletTargetsArgs', 'sst_tracklet_targets_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('boxes', 'ts', 'scores', 'trk_offsets', 'cand_boxes', 'cand_ts', 'cand_offsets',
+                                    'trk_cand_offsets', 'trk_class', 'chosen', 'counts', 'matched', 'overlaps',
+                                    'assigned_gt_inds', 'rois', 'src', 'frame_inds', 'gt_index', 'labels', 'iou_out',
+                                    'scores_out', 'soft_label', 'reg_mask', 'targets', 'pos_gt_bboxes')]
+    + [(k, c_i64) for k in ('n_rows', 'n_cand_rows', 'n_cands', 'n_tracklets')]
+    + [(k, _I32) for k in ('num_classes', 'object_centric')]
+    + [(k, ctypes.c_float) for k in ('candidate_thresh', 'iou_thr')]
+    + [(k, ctypes.c_double * 16) for k in ('cls_pos_thr', 'cls_neg_thr')]))
+TrackletRowsArgs = _struct('TrackletRowsArgs', 'sst_tracklet_rows_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('feats', 'xyz', 'pts_frame_inds', 'pts_inds', 'roi_inds', 'roi_frame_inds', 'roi_scores',
+                                    'out', 'xyz_out')]
+    + [(k, c_i64) for k in ('m', 'n_points', 'n_rois', 'ld_feats', 'ld_xyz')]
+    + [(k, _I32) for k in ('feat_cols', 'xyz_cols', 'combined', 'with_roi_scores')]))
 FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
@@ -483,6 +497,11 @@ _SIGNATURES = {
     'sst_optim_record_bytes': (c_i32, []),
     'sst_optim_workspace_bytes': (c_i64, [c_i64]),
     'sst_optim_step_f32': (c_i32, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_tracklet_targets_block': (c_i32, []),
+    'sst_tracklet_targets_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_tracklet_rows_fwd_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_tracklet_rows_keys_i64': (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    'sst_tracklet_rows_bwd_f32': (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

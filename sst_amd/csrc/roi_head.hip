@@ -21,6 +21,7 @@
 #include "common.h"
 #include "bev_clip.h"
 #include "head_math.h"
+#include "roi_target.h"
 
 namespace {
 
@@ -126,38 +127,6 @@ __global__ __launch_bounds__(kPolyBlock) void roi_assign_k(sst_roi_assign_args a
 // ------------------------------------------------------------------------------------------------------------------
 // the assigner's finish, the sampler, the targets: one workgroup per sample
 // ------------------------------------------------------------------------------------------------------------------
-
-// torch.remainder(x, m) for m > 0
-__device__ __forceinline__ float py_mod(float x, float m) {
-  float r = fmodf(x, m);
-  if (r != 0.f && r < 0.f) r += m;
-  return r;
-}
-
-// _get_target_single for one positive RoI and its box (fsd_bbox_head.py:420-447)
-__device__ __forceinline__ void roi_target_row(const float* roi, const float* g, float* t) {
-  const float roi_ry = py_mod(roi[6], kTwoPi);
-  const float cx = g[0] - roi[0], cy = g[1] - roi[1], cz = g[2] - roi[2];
-  const float cr = g[6] - roi_ry;
-  const float ang = -(roi_ry + kHalfPi);
-  const float sn = sinf(ang), cs = cosf(ang);
-  const float x = cx * cs + cy * sn, y = cy * cs - cx * sn;
-  float ry = py_mod(cr, kTwoPi);
-  if (ry > kHalfPi && ry < kPi * 1.5f) ry = py_mod(ry + kPi, kTwoPi);
-  if (ry > kPi) ry = ry - kTwoPi;
-  ry = fminf(fmaxf(ry, -kHalfPi), kHalfPi);
-  // DeltaXYZWLHRBBoxCoder.encode against the anchor (0, 0, 0, w, l, h, 0)
-  const float wa = roi[3], la = roi[4], ha = roi[5];
-  const float za = ha / 2, zg = cz + g[5] / 2;
-  const float diag = sqrtf(la * la + wa * wa);
-  t[0] = x / diag;
-  t[1] = y / diag;
-  t[2] = (zg - za) / ha;
-  t[3] = logf(g[3] / wa);
-  t[4] = logf(g[4] / la);
-  t[5] = logf(g[5] / ha);
-  t[6] = ry;
-}
 
 struct SampleLds {
   float key[kMaxProps];
