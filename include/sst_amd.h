@@ -2082,6 +2082,110 @@ int sst_tracklet_rows_keys_i64(const int64_t* d_pts_inds, int64_t m, int64_t n_p
 int sst_tracklet_rows_bwd_f32(const float* d_out_grad, int64_t m, int64_t ld_out, int feat_cols, const int64_t* d_sorted_keys,
                               int64_t n_points, float* d_feats_grad, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The FSD++ incremental point stage (csrc/incremental.hip): the input stage of TwoStageFSDPP for a whole batch - seed-box
+ * crops of the previous frames, capped per box, and the points of the current frame (and of frame -1) that fall into voxels
+ * no base frame occupies.  fp32 points, int64 frame indices, integer atomics only, bit-reproducible.
+ *
+ * Voxel coordinates everywhere below: incremental_ops.py:14-18 (voxelize_single), torch.div(p - lo, vs, rounding_mode =
+ * 'floor').int() in fp32 - torch's fmod-based floor division (c10::div_floor_floating), NOT floorf((p - lo) / vs): a = p - lo;
+ * mod = fmodf(a, vs); div = (a - mod) / vs; div -= 1 where mod != 0 and its sign differs from vs's; floor(div), + 1 where
+ * div - floor(div) > 0.5; a signed zero where div == 0.  Every operation is rounded on its own.
+ *
+ * sst_incr_voxel_coors_f32 - incremental_ops.py:14-18: d_points [n, >= 3] rows ld floats apart -> d_coors int32 [n, 3].
+ *
+ * sst_incr_mask_i32 - the TorchEx op incremental_points_mask(coors1, coors2, spatial_size) (call sites incremental_ops.py:62,
+ *   :121), with the set semantics of incremental_ops.py:20-34, :83-97 (find_delta_unq_coors + find_delta_pc_mask): mask[j] = 1
+ *   iff no row of coors1 equals row j of coors2.  An occupancy bitmap of spatial[0] * spatial[1] * spatial[2] bits (32-bit
+ *   atomicOr, skipped where the bit is already set); rows of coors1 outside the grid go to an overflow list (capacity n1) that
+ *   out-of-grid rows of coors2 are compared with exactly, so the answer is exact for every int32 triple.  One memset, two
+ *   launches.  Workspace: sst_incr_mask_workspace_bytes(n1, spatial) (< 0: the grid is refused).
+ *
+ * sst_incr_delta_mask_f32 - incremental_ops.py:45-63 (find_delta_points_by_voxelization) and :99-123
+ *   (find_delta_points_by_voxelization_list_v3) without the concatenation and the compactions: up to SST_INCR_MAX_CLOUDS base
+ *   clouds by value, one query cloud; mask[j] = 1 iff point j of the query falls into a voxel no base point falls into.
+ *   lower_bound != 0: v3's filter - points of either side that are not strictly above lo on every axis neither occupy nor
+ *   are new.  Workspace: sst_incr_mask_workspace_bytes(total base points, grid).
+ *
+ * sst_incr_plan_f32 + sst_incr_rows_f32 - two_stage_fsdpp.py:460-503 (generate_points), :592-635 (get_old_points), :637-678
+ *   (crop_and_process_points), :738-745 (get_delta_points) for every sample and frame of a batch.
+ *   Inputs: per sample s points[s] [n_points[s], cols] contiguous and frame_inds[s] int64 (0 = current, -k = k frames back);
+ *   boxes [n_boxes, 7] (already enlarged), box_offsets int32 [n_samples * n_frames + 1]: the boxes of (sample s, frame -(i + 1))
+ *   are rows box_offsets[s * n_frames + i] ..; keys uint32, one per point of the batch in sample order (NULL: the key is the
+ *   point's index); queries q < n_queries: the points with frame index q_inc[q] are tested against the points with frame
+ *   index in [q_lo[q], q_hi[q]] of the SAME sample (one bitmap per (sample, query)); a (sample, query) without a single base
+ *   point yields no delta row (get_delta_points, :740-743: an empty base cloud gives an empty result).
+ *   plan: one memset; mark (bits, overflow lists, the first box of its own (sample, frame) that holds a point - the inside test
+ *   of csrc/pib_test.h with the boxes staged in LDS, bit-equal to sst_points_in_boxes_f32 - and integer counts per box); with
+ *   max_crop_points > 0 a scan of the box counts, ONE sst_sort_pairs_u64 of (box << 32 | key) (stable: ties by point index) and
+ *   a rank launch (kept: rank in its box < max_crop_points = randperm + get_inner_win_inds < max_n for the permutation
+ *   argsort(keys)); flags and per-workgroup counts; a scan per (sample, segment).  It leaves counts int32
+ *   [n_samples, n_frames + n_queries] on the device: crop rows per frame, delta rows per query.
+ *   rows (after the caller has read counts and laid out the segments): out [M, cols + 1]; the rows of (sample s, segment b)
+ *   start at row seg_base[s * (n_frames + n_queries) + b], in ascending point index; the appended column is
+ *   float(-i - 1) / 10 for crop segment i (:626) and q_tag[q] for delta segment q (:483, :491).  Rows are staged in LDS and
+ *   leave as contiguous spans.  Workspace (the same buffer for both calls): sst_incr_workspace_bytes.
+ *
+ * sst_points_frame_transform_f32 - incremental_ops.py:175-186 (points_frame_transform) for up to SST_INCR_MAX_CLOUDS clouds
+ *   in one launch: dst[i] = (((x * m0 + y * m1) + z * m2) + m3 per row of the cloud's 3 x 4 matrix | the other columns), every
+ *   product and sum rounded on its own.  The matrix inv(cur_pose) @ pre_pose is formed by the caller.
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer, a negative size or a non-positive voxel size,
+ * SST_ERR_UNSUPPORTED for counts above the SST_INCR_* limits, cols outside 3..SST_INCR_MAX_COLS, a grid of more than 2^33
+ * cells or sizes above 2^31 - 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_INCR_MAX_SAMPLES 16
+#define SST_INCR_MAX_FRAMES 16
+#define SST_INCR_MAX_QUERIES 4
+#define SST_INCR_MAX_CLOUDS 8
+#define SST_INCR_MAX_COLS 15
+typedef struct sst_incr_args {
+  const float* points[SST_INCR_MAX_SAMPLES];
+  const int64_t* frame_inds[SST_INCR_MAX_SAMPLES];
+  int64_t n_points[SST_INCR_MAX_SAMPLES];
+  const float* boxes;
+  const int32_t* box_offsets;
+  const uint32_t* keys;
+  int32_t* counts;
+  float* out;
+  void* workspace;
+  int64_t workspace_bytes;
+  int64_t seg_base[SST_INCR_MAX_SAMPLES * (SST_INCR_MAX_FRAMES + SST_INCR_MAX_QUERIES)];
+  int32_t n_samples, cols, n_frames, n_queries, n_boxes, max_crop_points, lower_bound;
+  int32_t q_inc[SST_INCR_MAX_QUERIES], q_lo[SST_INCR_MAX_QUERIES], q_hi[SST_INCR_MAX_QUERIES];
+  float q_tag[SST_INCR_MAX_QUERIES];
+  float lo[3], vs[3];
+  int32_t grid[3];
+} sst_incr_args;
+typedef struct sst_incr_delta_args {
+  const float* base[SST_INCR_MAX_CLOUDS];
+  int64_t n_base[SST_INCR_MAX_CLOUDS], ld_base[SST_INCR_MAX_CLOUDS];
+  const float* query;
+  int64_t n_query, ld_query;
+  uint8_t* mask;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t n_clouds, lower_bound;
+  float lo[3], vs[3];
+  int32_t grid[3];
+} sst_incr_delta_args;
+typedef struct sst_frame_transform_args {
+  const float* src[SST_INCR_MAX_CLOUDS];
+  float* dst[SST_INCR_MAX_CLOUDS];
+  int64_t n[SST_INCR_MAX_CLOUDS];
+  float mat[SST_INCR_MAX_CLOUDS][12];
+  int32_t n_clouds, cols;
+} sst_frame_transform_args;
+int sst_incr_voxel_coors_f32(const float* d_points, int64_t n, int64_t ld, const float* lo3, const float* vs3, int32_t* d_coors,
+                             void* stream);
+int64_t sst_incr_mask_workspace_bytes(int64_t n_base, const int32_t* spatial3);
+int sst_incr_mask_i32(const int32_t* d_coors1, int64_t n1, const int32_t* d_coors2, int64_t n2, const int32_t* spatial3,
+                      void* d_workspace, int64_t workspace_bytes, uint8_t* d_mask, void* stream);
+int sst_incr_delta_mask_f32(const sst_incr_delta_args* args, void* stream);
+int64_t sst_incr_workspace_bytes(const sst_incr_args* args);
+int sst_incr_plan_f32(const sst_incr_args* args, void* stream);
+int sst_incr_rows_f32(const sst_incr_args* args, void* stream);
+int sst_points_frame_transform_f32(const sst_frame_transform_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

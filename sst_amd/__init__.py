@@ -70,10 +70,18 @@ from .tracklet import LiDARTracklet, TrackletAssigner, aligned_iou_3d, tracklet_
 from . import tracklet_detector  # noqa: F401
 from .tracklet_detector import (TimestampEncoder, TrackletDetector, TrackletPointRoIExtractor, TrackletRoIHead,  # noqa: F401
                                 TrackletSegmentor, get_bboxes_from_tracklet)
+from . import incremental  # noqa: F401
+from .incremental import (box_frame_transform_gpu, find_delta_points_by_voxelization,  # noqa: F401
+                          find_delta_points_by_voxelization_list_v3, generate_points, incremental_points_mask,
+                          points_frame_transform, seed_crop)
+from . import fsdpp  # noqa: F401
+from .fsdpp import TwoStageFSDPP  # noqa: F401
 
 __version__ = '0.1.0'
 
 __all__ = [
+    'incremental', 'box_frame_transform_gpu', 'find_delta_points_by_voxelization', 'find_delta_points_by_voxelization_list_v3',
+    'generate_points', 'incremental_points_mask', 'points_frame_transform', 'seed_crop', 'fsdpp', 'TwoStageFSDPP',
     'tracklet_detector', 'TimestampEncoder', 'TrackletDetector', 'TrackletPointRoIExtractor', 'TrackletRoIHead', 'TrackletSegmentor',
     'get_bboxes_from_tracklet', 'tracklet', 'LiDARTracklet', 'TrackletAssigner', 'aligned_iou_3d', 'tracklet_rows', 'tracklet_targets',
     'VirtualVoxelExtractor', 'detectors', 'DynamicVoxelNet', 'DynamicCenterPoint', 'install_fused_extract_feat', 'DETECTORS', 'HEADS', 'NECKS', 'FSD', 'FSDV2', 'SingleStageFSD', 'SingleStageFSDV2',

@@ -130,6 +130,21 @@ TrackletRowsArgs = _struct('TrackletRowsArgs', 'sst_tracklet_rows_args of includ
                                     'out', 'xyz_out')]
     + [(k, c_i64) for k in ('m', 'n_points', 'n_rois', 'ld_feats', 'ld_xyz')]
     + [(k, _I32) for k in ('feat_cols', 'xyz_cols', 'combined', 'with_roi_scores')]))
+IncrArgs = _struct('IncrArgs', 'sst_incr_args of include/sst_amd.h', (
+    [('points', ctypes.c_void_p * 16), ('frame_inds', ctypes.c_void_p * 16), ('n_points', c_i64 * 16)]
+    + [(k, ctypes.c_void_p) for k in ('boxes', 'box_offsets', 'keys', 'counts', 'out', 'workspace')]
+    + [('workspace_bytes', c_i64), ('seg_base', c_i64 * (16 * 20))]
+    + [(k, _I32) for k in ('n_samples', 'cols', 'n_frames', 'n_queries', 'n_boxes', 'max_crop_points', 'lower_bound')]
+    + [(k, _I32 * 4) for k in ('q_inc', 'q_lo', 'q_hi')]
+    + [('q_tag', ctypes.c_float * 4), ('lo', ctypes.c_float * 3), ('vs', ctypes.c_float * 3), ('grid', _I32 * 3)]))
+IncrDeltaArgs = _struct('IncrDeltaArgs', 'sst_incr_delta_args of include/sst_amd.h', (
+    [('base', ctypes.c_void_p * 8), ('n_base', c_i64 * 8), ('ld_base', c_i64 * 8), ('query', ctypes.c_void_p),
+     ('n_query', c_i64), ('ld_query', c_i64), ('mask', ctypes.c_void_p), ('workspace', ctypes.c_void_p),
+     ('workspace_bytes', c_i64), ('n_clouds', _I32), ('lower_bound', _I32), ('lo', ctypes.c_float * 3),
+     ('vs', ctypes.c_float * 3), ('grid', _I32 * 3)]))
+FrameTransformArgs = _struct('FrameTransformArgs', 'sst_frame_transform_args of include/sst_amd.h', (
+    [('src', ctypes.c_void_p * 8), ('dst', ctypes.c_void_p * 8), ('n', c_i64 * 8), ('mat', (ctypes.c_float * 12) * 8),
+     ('n_clouds', _I32), ('cols', _I32)]))
 FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
@@ -502,6 +517,14 @@ _SIGNATURES = {
     'sst_tracklet_rows_fwd_f32': (c_i32, [c_ptr, c_ptr]),
     'sst_tracklet_rows_keys_i64': (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     'sst_tracklet_rows_bwd_f32': (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_ptr]),
+    'sst_incr_voxel_coors_f32': (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_incr_mask_workspace_bytes': (c_i64, [c_i64, c_ptr]),
+    'sst_incr_mask_i32': (c_i32, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    'sst_incr_delta_mask_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_incr_workspace_bytes': (c_i64, [c_ptr]),
+    'sst_incr_plan_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_incr_rows_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_points_frame_transform_f32': (c_i32, [c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -27,6 +27,7 @@ from . import _lib
 from . import box_ops as _box
 from . import deform_conv as _dcn
 from . import fps as _fps
+from . import incremental as _incr
 from . import kernels as K
 from . import spconv as _spconv
 from . import voxel as _voxel
@@ -256,8 +257,9 @@ mmcv_deform_conv = types.SimpleNamespace(deform_conv2d=_deform_conv2d, DeformCon
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# TorchEx: boxes_overlap_1to1 only.  `from torchex import connected_components` must keep raising ImportError: the
-# reference falls back to scipy on it (single_stage_fsd.py:19-22).
+# TorchEx: boxes_overlap_1to1 and incremental_points_mask (incremental_ops.py:9-12).  `from torchex import connected_components`
+# must keep raising ImportError: the reference falls back to scipy on it (single_stage_fsd.py:19-22).
 # ------------------------------------------------------------------------------------------------------------------
-torchex = types.ModuleType('torchex', 'sst_amd stand-in for TorchEx: boxes_overlap_1to1 only')
+torchex = types.ModuleType('torchex', 'sst_amd stand-in for TorchEx: boxes_overlap_1to1 and incremental_points_mask')
 torchex.boxes_overlap_1to1 = _box.boxes_overlap_1to1
+torchex.incremental_points_mask = _incr.incremental_points_mask
