@@ -1120,7 +1120,19 @@ int64_t sst_spconv_conv_os_f32x6_workspace_bytes_rows(int kvol, int cin, int cou
 int sst_spconv_conv_os_rows_f32x6(const float* d_x, int64_t ldx, const int32_t* d_map, int64_t m, int kvol, const float* d_w,
                                   int cin, int cout, int trans_w, const float* d_bias, float* d_y, int64_t ldy, int tile_cfg,
                                   const int32_t* d_tile_order, void* d_workspace, int64_t workspace_bytes, void* stream);
-/*   sst_spconv_conv_os_plan: what a call of one of the four entries above would launch (host only, nothing runs): rows per
+/*   sst_spconv_conv_os_rows_bf16: the same contraction with bf16 OPERANDS - the gathered rows and the weights are rounded to
+ *     bf16 once (round to nearest even), one v_mfma_f32_16x16x32_bf16 product per pair, fp32 accumulation, fp32 result, fp32 in
+ *     memory (csrc/spconv_os_bf16.hip): the contraction of round_bf16(x) and round_bf16(w) up to the fp32 summation order, i.e. what
+ *     the f32x6 entries return on operands rounded beforehand.  The 'bf16' mode of sst_amd.spconv.SparseConvolution.  Argument
+ *     list, restrictions, launch order and offset split of sst_spconv_conv_os_rows_f32x6; the packed weights take 2 bytes per
+ *     element.  sst_spconv_conv_os_bf16_workspace_bytes_rows(kvol, cin, cout, m): packed weights + the partial tiles of the split
+ *     the call chooses for m rows (m = 0: the packed weights alone, the least a call accepts - SST_ERR_ARG below it; between the
+ *     two the split is halved until its partial tiles fit).  d_workspace 256-byte aligned.  Deterministic. */
+int64_t sst_spconv_conv_os_bf16_workspace_bytes_rows(int kvol, int cin, int cout, int64_t m);
+int sst_spconv_conv_os_rows_bf16(const float* d_x, int64_t ldx, const int32_t* d_map, int64_t m, int kvol, const float* d_w,
+                                 int cin, int cout, int trans_w, const float* d_bias, float* d_y, int64_t ldy, int tile_cfg,
+                                 const int32_t* d_tile_order, void* d_workspace, int64_t workspace_bytes, void* stream);
+/*   sst_spconv_conv_os_plan: what a call of one of the five entries above would launch (host only, nothing runs): rows per
  *     tile (64 | 128), columns per workgroup (64 | 128), the offset split the call really uses (after the rows entry's own
  *     halving against workspace_bytes; 1 for the others, which ignore workspace_bytes) and the workgroups launched (the
  *     padded grid).  Computed by the functions the launches call.  Same error codes as the entry for m, kvol, cin, cout,
@@ -1129,6 +1141,7 @@ int sst_spconv_conv_os_rows_f32x6(const float* d_x, int64_t ldx, const int32_t* 
 #define SST_SPCONV_OS_ENTRY_F32X3 1
 #define SST_SPCONV_OS_ENTRY_F32X6 2
 #define SST_SPCONV_OS_ENTRY_ROWS_F32X6 3
+#define SST_SPCONV_OS_ENTRY_ROWS_BF16 4
 int sst_spconv_conv_os_plan(int entry, int64_t m, int kvol, int cin, int cout, int tile_cfg, int64_t workspace_bytes,
                             int32_t* tile_rows, int32_t* cols, int32_t* n_split, int64_t* workgroups);
 /*   sst_spconv_wgrad_os_f32: the same filter gradient as sst_spconv_wgrad_f32 (indiceConvBackward, spconv_ops.h:359-446)
@@ -1148,6 +1161,12 @@ int sst_spconv_wgrad_os_plan(int kvol, int64_t pair_ld, int64_t total_pairs, int
 int sst_spconv_wgrad_os_f32x6(const float* d_x, int64_t ldx, const float* d_dy, int64_t lddy, const int32_t* d_pairs,
                             int64_t pair_ld, int64_t total_pairs, int x_side, const int32_t* d_num, int kvol, int cin,
                             int cout, float* d_dw, void* d_workspace, void* stream);
+/*   sst_spconv_wgrad_os_bf16: the same gradient with both gathered operands (x and dy) rounded to bf16 once, one product per pair on
+ *   the bf16 matrix pipe, fp32 accumulation, fp32 result (csrc/spconv_os_bf16.hip sp_wgrad_os_bf16_k): the filter-gradient half of
+ *   the 'bf16' convolution precision.  Same arguments, chunking (sst_spconv_wgrad_os_plan) and workspace as sst_spconv_wgrad_os_f32. */
+int sst_spconv_wgrad_os_bf16(const float* d_x, int64_t ldx, const float* d_dy, int64_t lddy, const int32_t* d_pairs,
+                             int64_t pair_ld, int64_t total_pairs, int x_side, const int32_t* d_num, int kvol, int cin,
+                             int cout, float* d_dw, void* d_workspace, void* stream);
 int64_t sst_spconv_wgrad_workspace_bytes(int kvol, int64_t pair_ld, int64_t total_pairs, int cin, int cout);
 int sst_spconv_wgrad_f32(const float* d_x, int64_t ldx, const float* d_dy, int64_t lddy, const int32_t* d_pairs,
                          int64_t pair_ld, int64_t total_pairs, int x_side, const int32_t* d_num, int kvol, int cin,

@@ -381,6 +381,11 @@ _SIGNATURES = {
                                               c_i32, c_ptr, c_ptr, c_i64, c_ptr]),
     'sst_spconv_conv_os_f32x6_workspace_bytes_rows': (c_i64, [c_i32, c_i32, c_i32, c_i64]),
     'sst_spconv_conv_os_f32x6_workspace_bytes': (c_i64, [c_i32, c_i32, c_i32]),
+    'sst_spconv_conv_os_bf16_workspace_bytes_rows': (c_i64, [c_i32, c_i32, c_i32, c_i64]),
+    'sst_spconv_conv_os_rows_bf16': (c_i32, [c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_i64,
+                                             c_i32, c_ptr, c_ptr, c_i64, c_ptr]),
+    'sst_spconv_wgrad_os_bf16': (c_i32, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i32, c_i32, c_i32,
+                                         c_ptr, c_ptr, c_ptr]),
     'sst_spconv_conv_os_plan': (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_spconv_wgrad_os_plan': (c_i32, [c_i32, c_i64, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
     'sst_spconv_os_tile_work_i32': (c_i32, [c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr]),

@@ -87,6 +87,13 @@ int sst_internal_spconv_x3_plan(int64_t m, int kvol, int cin, int cout, int32_t*
                                 int64_t* workgroups);
 int sst_internal_spconv_x6_plan(int rows, int64_t m, int kvol, int cin, int cout, int64_t workspace_bytes, int32_t* tile_rows,
                                 int32_t* cols, int32_t* n_split, int64_t* workgroups);
+// The bf16-operand sparse convolution (csrc/spconv_os_bf16.hip): the plan of its rows entry, and the launch of its filter-gradient
+// kernel for sst_spconv_wgrad_os_bf16 (csrc/spconv_os.hip checks the arguments, sizes the chunks and reduces the partials).
+int sst_internal_spconv_bf16_plan(int64_t m, int kvol, int cin, int cout, int64_t workspace_bytes, int32_t* tile_rows,
+                                  int32_t* cols, int32_t* n_split, int64_t* workgroups);
+void sst_internal_spconv_wgrad_bf16_launch(const float* d_x, int64_t ldx, const float* d_dy, int64_t lddy, const int32_t* d_pairs,
+                                           int64_t pair_ld, int x_side, const int32_t* d_num, int kvol, int cin, int cout,
+                                           int64_t chunks, int n_bi, int n_bj, int csize, float* d_part, void* stream);
 
 // Workspace carving on the host side (256-byte aligned slices of one caller-owned buffer).
 struct sst_carver {

@@ -787,6 +787,8 @@ int sst_spconv_conv_os_plan(int entry, int64_t m, int kvol, int cin, int cout, i
   if (entry == SST_SPCONV_OS_ENTRY_F32X6 || entry == SST_SPCONV_OS_ENTRY_ROWS_F32X6)
     return sst_internal_spconv_x6_plan(entry == SST_SPCONV_OS_ENTRY_ROWS_F32X6, m, kvol, cin, cout, workspace_bytes, tile_rows, cols,
                                        n_split, workgroups);
+  if (entry == SST_SPCONV_OS_ENTRY_ROWS_BF16)
+    return sst_internal_spconv_bf16_plan(m, kvol, cin, cout, workspace_bytes, tile_rows, cols, n_split, workgroups);
   return SST_ERR_ARG;
 }
 
@@ -846,7 +848,10 @@ static int wgrad_os_any(int split, const float* d_x, int64_t ldx, const float* d
   const int64_t chunks = os_wgrad_chunks(kvol, pair_ld, total_pairs, csize);
   if (kvol > 65535 || chunks > 0x7fffffff || n_bi * n_bj > 65535) return SST_ERR_UNSUPPORTED;
   float* part = (float*)d_workspace;
-  if (split)
+  if (split == 2)   // both gathered operands rounded to bf16, one product per pair (csrc/spconv_os_bf16.hip)
+    sst_internal_spconv_wgrad_bf16_launch(d_x, ldx, d_dy, lddy, d_pairs, pair_ld, x_side, d_num, kvol, cin, cout, chunks, n_bi, n_bj,
+                                          csize, part, stream);
+  else if (split)
     hipLaunchKernelGGL(sp_wgrad_os_x6_k, dim3((unsigned)chunks, (unsigned)(n_bi * n_bj)), dim3(256), 0, st, d_x, ldx, d_dy, lddy,
                        d_pairs, pair_ld, x_side, d_num, kvol, cin, cout, n_bj, csize, part);
   else
@@ -869,6 +874,13 @@ int sst_spconv_wgrad_os_f32x6(const float* d_x, int64_t ldx, const float* d_dy, 
                               int64_t pair_ld, int64_t total_pairs, int x_side, const int32_t* d_num, int kvol, int cin,
                               int cout, float* d_dw, void* d_workspace, void* stream) {
   return wgrad_os_any(1, d_x, ldx, d_dy, lddy, d_pairs, pair_ld, total_pairs, x_side, d_num, kvol, cin, cout, d_dw, d_workspace,
+                      stream);
+}
+
+int sst_spconv_wgrad_os_bf16(const float* d_x, int64_t ldx, const float* d_dy, int64_t lddy, const int32_t* d_pairs,
+                             int64_t pair_ld, int64_t total_pairs, int x_side, const int32_t* d_num, int kvol, int cin,
+                             int cout, float* d_dw, void* d_workspace, void* stream) {
+  return wgrad_os_any(2, d_x, ldx, d_dy, lddy, d_pairs, pair_ld, total_pairs, x_side, d_num, kvol, cin, cout, d_dw, d_workspace,
                       stream);
 }
 

@@ -10,9 +10,10 @@ Only 3-D (``ndim=3``) is built.
 import torch
 from torch import nn
 
+from . import _lib
 from .norm import batch_norm_act, build_conv_layer, build_norm_layer
 from .registry import BACKBONES, MIDDLE_ENCODERS
-from .spconv import SparseConvTensor, SparseModule, SparseSequential
+from .spconv import SparseConvTensor, SparseConvolution, SparseModule, SparseSequential, set_module_precision
 
 
 def replace_feature(out, new_features):
@@ -98,13 +99,32 @@ def make_sparse_convmodule(in_channels, out_channels, kernel_size, indice_key, s
     return SparseSequential(*[make[kind]() for kind in order])
 
 
-class _UNetStages(nn.Module):
+class _UNetStages(_lib.Fp32Master, nn.Module):
     """What SparseUNet, SimpleSparseUNet and VirtualVoxelMixer share (sparse_unet.py:16-321): the input convolution, an
     encoder of submanifold stages (every stage after the first opened by a stride-2 convolution), and a decoder that
     walks back up - lateral residual block, concatenation with the coarser feature, merge convolution, channel-folded
     residual, inverse convolution onto the finer level's voxels.  Sub-module names are the reference's (they are the
     ``state_dict`` keys): conv_input, encoder_layers.encoder_layer{i}, lateral_layer{i}, merge_layer{i},
-    upsample_layer{i}."""
+    upsample_layer{i}.
+
+    Reduced precision: ``set_precision('bf16')`` runs every convolution of the network with bf16 operands (fp32 accumulation,
+    storage, batch norm and master weights: spconv.SparseConvolution).  The reference's fp16 key (``model.half()`` /
+    ``fp16_enabled``) means the same here (_lib.Fp32Master): parameters and buffers stay fp32, half features are taken in
+    through as_fp32, the convolutions without a precision of their own run at 'bf16', and the features are handed on as float16."""
+
+    def set_precision(self, mode):
+        """the convolution precision of every sparse convolution the network owns (spconv.MODULE_PRECISIONS) -> self"""
+        return set_module_precision(self, mode)
+
+    def _half_mode(self):
+        """was the fp16 mode asked for; the convolutions are told once per change (an explicit set_precision wins over it)"""
+        half = _lib.wants_half(self)
+        if half != self.__dict__.get('_sst_auto_half', False):
+            for m in self.modules():
+                if isinstance(m, SparseConvolution):
+                    m._auto_precision = 'bf16' if half else None
+            self.__dict__['_sst_auto_half'] = half
+        return half
 
     def _build_stages(self, in_channels, sparse_shape, order, norm_cfg, base_channels, output_channels, encoder_channels,
                       encoder_paddings, decoder_channels, decoder_paddings, ndim, act_type, init_cfg):
@@ -166,7 +186,8 @@ class _UNetStages(nn.Module):
     def encode(self, voxel_features, coors, batch_size, indice_dict=None):
         """-> the feature of every encoder level, finest first; indice_dict: rulebooks built ahead (build_rulebooks) for
         exactly these coordinates"""
-        first = SparseConvTensor(voxel_features, coors.int(), self.sparse_shape, batch_size)
+        self._half_mode()
+        first = SparseConvTensor(_lib.as_fp32(voxel_features), coors.int(), self.sparse_shape, batch_size)
         if indice_dict is not None:
             first.indice_dict = indice_dict
         x = self.conv_input(first)
@@ -231,7 +252,10 @@ class SparseUNet(_UNetStages):
         dense = self.conv_out(levels[-1]).dense()
         n, c, d, h, w = dense.shape
         finest, _ = self.decode(levels)
-        return dict(spatial_features=dense.view(n, c * d, h, w), seg_features=finest.features)
+        spatial, seg = dense.view(n, c * d, h, w), finest.features
+        if self._half_mode():
+            spatial, seg = spatial.half(), seg.half()
+        return dict(spatial_features=spatial, seg_features=seg)
 
 
 @BACKBONES.register_module()
@@ -261,7 +285,8 @@ class SimpleSparseUNet(_UNetStages):
             batch_size = int(coors[:, 0].max().item()) + 1
         finest, every = self.decode(self.encode(voxel_info['voxel_feats'], coors, batch_size, voxel_info.get('indice_dict')),
                                     keep_all=self.return_multiscale_features)
-        return [{'voxel_feats': finest.features, 'voxel_coors': finest.indices, 'sparse_shape': finest.spatial_shape,
+        feats = finest.features.half() if self._half_mode() else finest.features
+        return [{'voxel_feats': feats, 'voxel_coors': finest.indices, 'sparse_shape': finest.spatial_shape,
                  'batch_size': finest.batch_size, 'decoder_features': every}]
 
 
@@ -288,4 +313,4 @@ class VirtualVoxelMixer(_UNetStages):
             coors = coors[:, self.keep_coors_dims]
         finest, _ = self.decode(self.encode(voxel_features, coors, batch_size))
         out = self.conv_out(finest)
-        return out.features, out.indices, out.spatial_shape
+        return (out.features.half() if self._half_mode() else out.features), out.indices, out.spatial_shape

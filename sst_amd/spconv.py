@@ -314,7 +314,10 @@ def set_conv_precision(mode):
       'f32x6'  (default) exact three-way bf16 split of both operands, six products, fp32 accumulation (csrc/spconv_os_x6.hip): the same
                arithmetic class (error vs float64 <= 2 x the fp32 kernel's, tests/test_gpu_spconv.py), 2.7 x less pipe time;
       'f32x3'  two-way split, three products (csrc/spconv_os_x3.hip; ~1e-5 of the output scale per layer): a leg only.
-    PROCESS-GLOBAL, like sst_amd.dense.set_matmul_mode."""
+    PROCESS-GLOBAL, like sst_amd.dense.set_matmul_mode.
+    'bf16' (bf16 operands, one product: csrc/spconv_os_bf16.hip) is NOT a value of this switch and keeps raising ValueError here:
+    the global mode decides what every model of the process - the bench lines among them - computes, and a reduced-precision
+    mode is chosen per module (SparseConvolution.set_precision, set_module_precision, the U-Nets' set_precision)."""
     global _CONV_PRECISION
     if mode not in ('f32', 'f32x3', 'f32x6'):
         raise ValueError(mode)
@@ -325,10 +328,27 @@ def conv_precision():
     return _CONV_PRECISION
 
 
-def _gather_gemm(x, mapping, rows, weight3, trans_w, cout, density=None, tile_cfg=0):
+# what a module (or the `precision` argument of the functional layer) may ask for; None = the global mode
+MODULE_PRECISIONS = (None, 'f32', 'f32x3', 'f32x6', 'bf16')
+
+
+def _check_precision(mode):
+    if mode not in MODULE_PRECISIONS:
+        raise ValueError(mode)
+    return mode
+
+
+def round_bf16(t):
+    """fp32 -> the nearest bf16 value (ties to even), as fp32: the operand rounding of the 'bf16' mode"""
+    return t.to(torch.bfloat16).to(torch.float32)
+
+
+def _gather_gemm(x, mapping, rows, weight3, trans_w, cout, density=None, tile_cfg=0, precision=None):
     # density: a number, None, or the Rulebook (its `density` costs a host read-back: only the legacy path asks for it)
-    """Y[r] = sum_k X[mapping[k][r]] W[k]; weight3 is [K, cin, cout], or [K, cout, cin] with trans_w."""
+    """Y[r] = sum_k X[mapping[k][r]] W[k]; weight3 is [K, cin, cout], or [K, cout, cin] with trans_w.
+    precision: None (the global mode) or one of MODULE_PRECISIONS."""
     lib = _lib.load()
+    mode = _CONV_PRECISION if precision is None else _check_precision(precision)
     x = x if x.stride(1) == 1 else x.contiguous()
     if x.size(0) == 0:   # nothing to gather from (e.g. the data gradient of a layer whose output side is empty)
         return torch.zeros((rows, cout), dtype=torch.float32, device=x.device)
@@ -337,9 +357,25 @@ def _gather_gemm(x, mapping, rows, weight3, trans_w, cout, density=None, tile_cf
         return y
     kvol, cin = weight3.size(0), x.size(1)
     weight3 = weight3 if weight3.is_contiguous() else weight3.contiguous()
-    if (_conv_kernel_choice() == 'os' and kvol <= 32 and cin % 4 == 0 and x.stride(0) % 4 == 0
-            and x.data_ptr() % 16 == 0):
-        split = _CONV_PRECISION if (_CONV_PRECISION != 'f32' and int(tile_cfg) == 0) else None
+    os_ok = (_conv_kernel_choice() == 'os' and kvol <= 32 and cin % 4 == 0 and x.stride(0) % 4 == 0
+             and x.data_ptr() % 16 == 0)
+    if mode == 'bf16':
+        if os_ok and int(tile_cfg) == 0:
+            ws = _lib.workspace(lib.sst_spconv_conv_os_bf16_workspace_bytes_rows(kvol, cin, cout, rows), x.device)
+            order = None
+            if isinstance(density, Rulebook) and rows >= _OS_ORDER_MIN_ROWS and _os_tile_order_enabled():
+                order = density.tile_order(mapping, rows, 64)
+            rc = lib.sst_spconv_conv_os_rows_bf16(_lib.ptr(x), x.stride(0), _lib.ptr(mapping), rows, kvol, _lib.ptr(weight3), cin,
+                                                  cout, int(trans_w), None, _lib.ptr(y), y.stride(0), 0,
+                                                  _lib.ptr(order) if order is not None else None, _lib.ptr(ws), ws.numel(),
+                                                  _lib.stream_ptr())
+            _lib.check(rc, 'sst_spconv_conv_os_rows_bf16')
+            return y
+        # a shape the bf16 entry refuses: the SAME quantity from operands rounded here and the exact-split arithmetic (the exact
+        # split of a bf16 value is that value) - never another arithmetic
+        x, weight3, mode = round_bf16(x), round_bf16(weight3), 'f32x6'
+    if os_ok:
+        split = mode if (mode != 'f32' and int(tile_cfg) == 0) else None
         if split == 'f32x6':     # room for the partial tiles of a thin level too (csrc/spconv_os_x6.hip: offsets dealt out)
             ws = _lib.workspace(lib.sst_spconv_conv_os_f32x6_workspace_bytes_rows(kvol, cin, cout, rows), x.device)
         else:
@@ -377,20 +413,27 @@ def _gather_gemm(x, mapping, rows, weight3, trans_w, cout, density=None, tile_cf
     return y
 
 
-def _wgrad(x, dy, rb, pairs, x_side, shape):
+def _wgrad(x, dy, rb, pairs, x_side, shape, precision=None):
     lib = _lib.load()
+    mode = _CONV_PRECISION if precision is None else _check_precision(precision)
     kvol, cin, cout = rb.kvol, x.size(1), dy.size(1)
     dw = torch.empty((kvol, cin, cout), dtype=torch.float32, device=x.device)
     x = x if x.stride(1) == 1 else x.contiguous()
     dy = dy if dy.stride(1) == 1 else dy.contiguous()
     ldx, lddy = (x.stride(0) if x.size(0) else cin), (dy.stride(0) if dy.size(0) else cout)
     total = rb.known_total_pairs()     # -1 while nobody has read the count back: launch and workspace use the upper bound
-    if (_conv_kernel_choice() == 'os' and cin % 4 == 0 and cout % 4 == 0 and ldx % 4 == 0 and lddy % 4 == 0
-            and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0):
+    os_ok = (_conv_kernel_choice() == 'os' and cin % 4 == 0 and cout % 4 == 0 and ldx % 4 == 0 and lddy % 4 == 0
+             and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
+    if mode == 'bf16' and not os_ok:
+        # a shape the bf16 entry refuses: both gathered operands rounded here, then the existing path at 'f32x6' (the same quantity)
+        x, dy, mode = round_bf16(x), round_bf16(dy), 'f32x6'
+        ldx, lddy = (x.stride(0) if x.size(0) else cin), (dy.stride(0) if dy.size(0) else cout)
+    if os_ok:
         ws = _lib.workspace(lib.sst_spconv_wgrad_os_workspace_bytes(kvol, rb.n, total, cin, cout), x.device)
-        # the filter gradient multiplies the way the convolution does: exact three-way bf16 split ('f32x6', the default) or the
-        # fp32 matrix pipe ('f32'; 'f32x3' has no filter-gradient kernel of its own and takes the fp32 one)
-        name = ('sst_spconv_wgrad_os_f32x6' if (_CONV_PRECISION == 'f32x6' and os.environ.get('SST_SPCONV_WGRAD_X6', '1') != '0')
+        # the filter gradient multiplies the way the convolution does: exact three-way bf16 split ('f32x6', the default), bf16
+        # operands ('bf16') or the fp32 matrix pipe ('f32'; 'f32x3' has no filter-gradient kernel of its own and takes the fp32 one)
+        name = ('sst_spconv_wgrad_os_bf16' if mode == 'bf16' else
+                'sst_spconv_wgrad_os_f32x6' if (mode == 'f32x6' and os.environ.get('SST_SPCONV_WGRAD_X6', '1') != '0')
                 else 'sst_spconv_wgrad_os_f32')     # SST_SPCONV_WGRAD_X6=0: A/B against the fp32-pipe kernel
         rc = getattr(lib, name)(_lib.ptr(x), ldx, _lib.ptr(dy), lddy, _lib.ptr(pairs), rb.n, total, x_side,
                                 _lib.ptr(rb.num), kvol, cin, cout, _lib.ptr(dw), _lib.ptr(ws), _lib.stream_ptr())
@@ -410,29 +453,30 @@ def _check(features, filters):
         raise NotImplementedError('sst_amd.spconv: fp32 only')
 
 
-def indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, inverse=False, subm=False):
-    """ops.py:105-124: out[pairs[k][1 - inverse]] += features[pairs[k][inverse]] @ filters[k]"""
+def indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, inverse=False, subm=False, precision=None):
+    """ops.py:105-124: out[pairs[k][1 - inverse]] += features[pairs[k][inverse]] @ filters[k]
+    precision: None (the global mode, set_conv_precision) or one of MODULE_PRECISIONS"""
     _check(features, filters)
     rb = rulebook_of(indice_pairs, indice_pair_num, features.size(0) if inverse else num_activate_out)
     w3 = filters.reshape(-1, filters.shape[-2], filters.shape[-1])
     if inverse:
-        return _gather_gemm(features, rb.in2out, rb.n, w3, False, w3.size(2), rb)
-    return _gather_gemm(features, rb.out2in, rb.m, w3, False, w3.size(2), rb)
+        return _gather_gemm(features, rb.in2out, rb.n, w3, False, w3.size(2), rb, precision=precision)
+    return _gather_gemm(features, rb.out2in, rb.m, w3, False, w3.size(2), rb, precision=precision)
 
 
-def indice_conv_backward(features, filters, out_bp, indice_pairs, indice_pair_num, inverse=False, subm=False):
-    """ops.py:139-156 -> (input gradient, filter gradient)"""
+def indice_conv_backward(features, filters, out_bp, indice_pairs, indice_pair_num, inverse=False, subm=False, precision=None):
+    """ops.py:139-156 -> (input gradient, filter gradient); precision as indice_conv's"""
     _check(features, filters)
     rb = rulebook_of(indice_pairs, indice_pair_num, features.size(0) if inverse else out_bp.size(0))
     w3 = filters.reshape(-1, filters.shape[-2], filters.shape[-1])
     out_bp = out_bp.contiguous()
     # the data gradient is the same contraction with W[k]^T: the forward weights are read with the roles swapped
     if inverse:
-        input_bp = _gather_gemm(out_bp, rb.out2in, rb.m, w3, True, w3.size(1), rb)
-        filters_bp = _wgrad(features, out_bp, rb, indice_pairs, 1, filters.shape)
+        input_bp = _gather_gemm(out_bp, rb.out2in, rb.m, w3, True, w3.size(1), rb, precision=precision)
+        filters_bp = _wgrad(features, out_bp, rb, indice_pairs, 1, filters.shape, precision)
     else:
-        input_bp = _gather_gemm(out_bp, rb.in2out, rb.n, w3, True, w3.size(1), rb)
-        filters_bp = _wgrad(features, out_bp, rb, indice_pairs, 0, filters.shape)
+        input_bp = _gather_gemm(out_bp, rb.in2out, rb.n, w3, True, w3.size(1), rb, precision=precision)
+        filters_bp = _wgrad(features, out_bp, rb, indice_pairs, 0, filters.shape, precision)
     return input_bp, filters_bp
 
 
@@ -494,45 +538,11 @@ indice_maxpool_fn = SparseMaxPoolFunction.apply
 class SparseConvFunction(torch.autograd.Function):
 
     @staticmethod
-    def forward(ctx, features, filters, indice_pairs, indice_pair_num, num_activate_out):
+    def forward(ctx, features, filters, indice_pairs, indice_pair_num, num_activate_out, precision=None):
         ctx.save_for_backward(indice_pairs, indice_pair_num, features, filters)
+        ctx.precision = precision
         ctx.rulebook = getattr(indice_pairs, '_sst_rulebook', None)
-        return indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, False)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        indice_pairs, indice_pair_num, features, filters = ctx.saved_tensors
-        if ctx.rulebook is not None:
-            indice_pairs._sst_rulebook = ctx.rulebook
-        input_bp, filters_bp = indice_conv_backward(features, filters, grad_output, indice_pairs, indice_pair_num, False)
-        return input_bp, filters_bp, None, None, None
-
-
-class SparseInverseConvFunction(torch.autograd.Function):
-
-    @staticmethod
-    def forward(ctx, features, filters, indice_pairs, indice_pair_num, num_activate_out):
-        ctx.save_for_backward(indice_pairs, indice_pair_num, features, filters)
-        ctx.rulebook = getattr(indice_pairs, '_sst_rulebook', None)
-        return indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, True, False)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        indice_pairs, indice_pair_num, features, filters = ctx.saved_tensors
-        if ctx.rulebook is not None:
-            indice_pairs._sst_rulebook = ctx.rulebook
-        input_bp, filters_bp = indice_conv_backward(features, filters, grad_output, indice_pairs, indice_pair_num, True,
-                                                    False)
-        return input_bp, filters_bp, None, None, None
-
-
-class SubMConvFunction(torch.autograd.Function):
-
-    @staticmethod
-    def forward(ctx, features, filters, indice_pairs, indice_pair_num, num_activate_out):
-        ctx.save_for_backward(indice_pairs, indice_pair_num, features, filters)
-        ctx.rulebook = getattr(indice_pairs, '_sst_rulebook', None)
-        return indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, False, True)
+        return indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, False, precision=precision)
 
     @staticmethod
     def backward(ctx, grad_output):
@@ -540,8 +550,46 @@ class SubMConvFunction(torch.autograd.Function):
         if ctx.rulebook is not None:
             indice_pairs._sst_rulebook = ctx.rulebook
         input_bp, filters_bp = indice_conv_backward(features, filters, grad_output, indice_pairs, indice_pair_num, False,
-                                                    True)
-        return input_bp, filters_bp, None, None, None
+                                                    precision=ctx.precision)
+        return input_bp, filters_bp, None, None, None, None
+
+
+class SparseInverseConvFunction(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, features, filters, indice_pairs, indice_pair_num, num_activate_out, precision=None):
+        ctx.save_for_backward(indice_pairs, indice_pair_num, features, filters)
+        ctx.precision = precision
+        ctx.rulebook = getattr(indice_pairs, '_sst_rulebook', None)
+        return indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, True, False, precision)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        indice_pairs, indice_pair_num, features, filters = ctx.saved_tensors
+        if ctx.rulebook is not None:
+            indice_pairs._sst_rulebook = ctx.rulebook
+        input_bp, filters_bp = indice_conv_backward(features, filters, grad_output, indice_pairs, indice_pair_num, True,
+                                                    False, ctx.precision)
+        return input_bp, filters_bp, None, None, None, None
+
+
+class SubMConvFunction(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, features, filters, indice_pairs, indice_pair_num, num_activate_out, precision=None):
+        ctx.save_for_backward(indice_pairs, indice_pair_num, features, filters)
+        ctx.precision = precision
+        ctx.rulebook = getattr(indice_pairs, '_sst_rulebook', None)
+        return indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_out, False, True, precision)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        indice_pairs, indice_pair_num, features, filters = ctx.saved_tensors
+        if ctx.rulebook is not None:
+            indice_pairs._sst_rulebook = ctx.rulebook
+        input_bp, filters_bp = indice_conv_backward(features, filters, grad_output, indice_pairs, indice_pair_num, False,
+                                                    True, ctx.precision)
+        return input_bp, filters_bp, None, None, None, None
 
 
 indice_conv_fn = SparseConvFunction.apply
@@ -653,7 +701,18 @@ def _calculate_fan_in_and_fan_out_hwio(tensor):
 
 
 class SparseConvolution(SparseModule):
-    """conv.py:49-230.  fused_bn is accepted and ignored (the reference marks it "don't use")."""
+    """conv.py:49-230.  fused_bn is accepted and ignored (the reference marks it "don't use").
+
+    ``precision``: how THIS layer's forward contraction, data gradient and filter gradient multiply - None (the process-global
+    mode of set_conv_precision, the default), 'f32', 'f32x3', 'f32x6' or 'bf16' (operands rounded to bf16 once, one product,
+    fp32 accumulation and results, csrc/spconv_os_bf16.hip; weights and their gradients stay the fp32 masters)."""
+
+    precision = None
+    _auto_precision = None   # set by an owning Fp32Master backbone after ``.half()`` (sparse_unet._UNetStages); `precision` wins
+
+    def set_precision(self, mode):
+        self.precision = _check_precision(mode)
+        return self
 
     def __init__(self, ndim, in_channels, out_channels, kernel_size=3, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, subm=False, output_padding=0, transposed=False, inverse=False, indice_key=None,
@@ -742,8 +801,12 @@ class SparseConvolution(SparseModule):
         assert isinstance(input, SparseConvTensor)
         features = input.features
         batch_size = input.batch_size
+        precision = self.precision if self.precision is not None else self._auto_precision
         if self.conv1x1:
-            features = torch.mm(input.features, self.weight.view(self.in_channels, self.out_channels))
+            weight = self.weight.view(self.in_channels, self.out_channels)
+            if precision == 'bf16':   # the same definition: operands rounded once, products exact in fp32, fp32 sums
+                features, weight = round_bf16(features), round_bf16(weight)
+            features = torch.mm(features, weight)
             if self.bias is not None:
                 features += self.bias
             out_tensor = SparseConvTensor(features, input.indices, input.spatial_shape, input.batch_size)
@@ -751,18 +814,25 @@ class SparseConvolution(SparseModule):
             out_tensor.grid = input.grid
             return out_tensor
         outids, indice_pairs, indice_pair_num, out_spatial_shape = self._geometry(input)
-        if self.subm:
-            out_features = indice_subm_conv(features, self.weight, indice_pairs, indice_pair_num, outids.shape[0])
-        elif self.inverse:
-            out_features = indice_inverse_conv(features, self.weight, indice_pairs, indice_pair_num, outids.shape[0])
-        else:
-            out_features = indice_conv_fn(features, self.weight, indice_pairs, indice_pair_num, outids.shape[0])
+        fn = indice_subm_conv if self.subm else (indice_inverse_conv if self.inverse else indice_conv_fn)
+        out_features = fn(features, self.weight, indice_pairs, indice_pair_num, outids.shape[0], precision)
         if self.bias is not None:
             out_features += self.bias
         out_tensor = SparseConvTensor(out_features, outids, out_spatial_shape, batch_size)
         out_tensor.indice_dict = input.indice_dict
         out_tensor.grid = input.grid
         return out_tensor
+
+
+def set_module_precision(module, mode):
+    """``set_precision(mode)`` on every sparse convolution inside ``module`` (any container: a U-Net, a detector's
+    ``segmentor``, a whole detector); -> module.  mode: one of MODULE_PRECISIONS (None = back to the global mode)."""
+    _check_precision(mode)
+    for m in module.modules():
+        if isinstance(m, SparseConvolution):
+            m.set_precision(mode)
+    return module
+
 
 @CONV_LAYERS.register_module()
 class SparseConv3d(SparseConvolution):
