@@ -8,14 +8,19 @@
 // smallest node index they contain.
 //
 // Here: lock-free union-find over all samples at once.  cc_pairs_k enumerates the pairs (j < i) tile by tile
-// (256 x 256, the j tile staged in LDS), tests `same sample && sqrt(dx*dx + dy*dy) < dist` with the reference's
-// own fp32 operations (separate multiplies, add, correctly rounded sqrt: no FMA contraction, so the edge set is
-// bit-identical), and hooks the LARGER root under the smaller one with atomicCAS.  The root of a component is
+// (256 x 256, the j tile staged in LDS), tests `same sample && sqrt(dx*dx + dy*dy) < dist` as the reference's tensor
+// operations and their numpy float32 restatement evaluate it: subtract, two products, one sum, each rounded on its own
+// (plain operators that may not be contracted: `#pragma clang fp contract(off)` in exact_math.h and -ffp-contract=off
+// for this file in the Makefile), then the correctly rounded root (sst_sqrt_rn: the fp64 root rounded once more, not
+// __fsqrt_rn, which is the approximate v_sqrt_f32 in this build).  So the edge set is bit-identical: pinned at the
+// thresholds' own ulps by tests/test_gpu_cluster_boundary.py.  It hooks the LARGER root under the smaller one with
+// atomicCAS.  The root of a component is
 // therefore its smallest node index whatever the execution order: flatten, flag the roots, exclusive-scan the
 // flags and label[i] = rank of root(i) — scipy's numbering, deterministic.  With samples stored one after the
 // other (they are: the centres come out of a sorted-unique) this also equals the reference's per-sample
 // numbering with a running base.  N is a few 1e3..1e4 centres: the N^2/2 pair tests are ~1e8 simple operations.
 #include "common.h"
+#include "exact_math.h"
 
 namespace {
 
@@ -86,9 +91,7 @@ __global__ __launch_bounds__(kCcTile) void cc_pairs_k(const float* __restrict__ 
     const int j = j0 + q;
     if (j >= i) break;  // lower triangle only (the graph is undirected)
     if (bs[q] != bi) continue;
-    const float dx = __fsub_rn(xi, xs[q]), dy = __fsub_rn(yi, ys[q]);
-    const float d = __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-    if (d < dist) cc_union(parent, i, j);
+    if (sst_xy_dist(xi, yi, xs[q], ys[q]) < dist) cc_union(parent, i, j);
   }
 }
 

@@ -20,12 +20,16 @@
 //               the winner is the k with the smallest (bitreverse_{log2 B}(k mod B), k div B).  That pair, as one 32-bit
 //               number, is the rank.  B comes from the SEGMENT's length.
 //   arithmetic  d = (x2-x1)*(x2-x1) + (y2-y1)*(y2-y1) + (z2-z1)*(z2-z1), left to right, every product and sum rounded on
-//               its own (-ffp-contract=off and explicit __f*_rn): the form a numpy float32 restatement reproduces.
+//               its own: plain operators under -ffp-contract=off (the __f*_rn names this toolchain gives them ARE the plain
+//               operators and pin nothing, exact_math.h): the form a numpy float32 restatement reproduces.
 //   ssg_*_k     pruning (parallel K x K: keypoint j falls if ANY earlier keypoint of its segment is closer than thr2),
 //               numbering (exclusive scan of the surviving flags over all segments) and assignment (every point counts the
 //               surviving keypoints of its segment closer than radius; exactly one -> its id, else -1), keypoints staged
-//               through LDS one per lane; no [K, N] matrix.  sqrt(dx*dx + dy*dy) with the reference's own operations.
+//               through LDS one per lane; no [K, N] matrix.  sqrt(dx*dx + dy*dy) is sst_xy_dist of exact_math.h: separately
+//               rounded operations and the correctly rounded root (the fp64 root rounded once more; __fsqrt_rn is the
+//               approximate v_sqrt_f32 in this build and decided pairs on the threshold wrongly).
 #include "common.h"
+#include "exact_math.h"
 
 namespace {
 
@@ -91,8 +95,9 @@ __device__ __forceinline__ void fps_argmax(FpsSlots& s, int buf, u64 best, float
 }
 
 __device__ __forceinline__ float fps_sqdist(float x2, float y2, float z2, float x1, float y1, float z1) {
-  const float dx = __fsub_rn(x2, x1), dy = __fsub_rn(y2, y1), dz = __fsub_rn(z2, z1);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+  const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;  // no contraction: exact_math.h's pragma and the Makefile's flag
+  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  return (xx + yy) + zz;
 }
 
 // low word of the key of this thread's point 0 (k = t); point i (k = t + 1024 i) has low word - i.  n >= 1.
@@ -228,10 +233,7 @@ __global__ __launch_bounds__(kFpsThreads) void fps_k(const float* __restrict__ d
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kSsgTile = 256;
 
-__device__ __forceinline__ float ssg_dist(float ax, float ay, float bx, float by) {
-  const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by);
-  return __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-}
+__device__ __forceinline__ float ssg_dist(float ax, float ay, float bx, float by) { return sst_xy_dist(ax, ay, bx, by); }
 
 // blockIdx.y = segment, blockIdx.x = tile of 256 keypoints j; the earlier keypoints i < j pass through LDS tile by tile
 __global__ __launch_bounds__(kSsgTile) void ssg_prune_k(const float* __restrict__ pts, int64_t ld,

@@ -5,6 +5,7 @@
 #pragma once
 #include <math.h>
 #include "common.h"
+#include "exact_math.h"  // sst_sqrt_rn, the correctly rounded root (shared with the clustering kernels)
 
 // the functions below round operation by operation whatever file includes them
 #pragma clang fp contract(off)
@@ -101,10 +102,6 @@ __device__ __forceinline__ float sst_reg_elem(float d, float beta) {
 __device__ __forceinline__ float sst_reg_grad(float d, float beta) {
   return fabsf(d) < beta ? d / beta : d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f;
 }
-
-// The correctly rounded fp32 root.  __fsqrt_rn is the approximate v_sqrt_f32 in a default build; the fp64 root of an fp32
-// number, rounded to fp32, is exact rounding (53 >= 2 * 24 + 2 bits) whatever the build flags are.
-__device__ __forceinline__ float sst_sqrt_rn(float v) { return (float)sqrt((double)v); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // the [class][row] LDS image of the row kernels
