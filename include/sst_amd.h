@@ -2205,6 +2205,87 @@ int sst_incr_plan_f32(const sst_incr_args* args, void* stream);
 int sst_incr_rows_f32(const sst_incr_args* args, void* stream);
 int sst_points_frame_transform_f32(const sst_frame_transform_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training augmentation of points and boxes (csrc/augment.hip): what a shipped train_pipeline does after
+ * db_sampler.sample_all - ObjectSample's point removal (mmdet3d/datasets/pipelines/transforms_3d.py:262-279, :332-334),
+ * RandomFlip3D (:95-172), GlobalRotScaleTrans (:564-676), PointsRangeFilter, ObjectRangeFilter and PointShuffle - for a packed
+ * batch.  fp32, every operation rounded on its own (no contraction), integer atomics only, bit-reproducible.
+ *
+ * sst_augment_params - one record per sample: flags flip_h, flip_v, rotate, shuffle; cos, sin of the fp32 angle, scale, the
+ *   angle itself (boxes: yaw += angle); trans[3]; range[6] = (x0, y0, z0, x1, y1, z1); the 64-bit shuffle seed.
+ *
+ * sst_augment_points_f32 - points [n_total, cols] (3 <= cols <= SST_AUG_MAX_COLS, 16-byte aligned), sample after sample, inside
+ *   a sample the n_pasted[s] pasted rows first (points.cat([sampled_points, points]), :334); row_offsets int64 [batch + 1];
+ *   block_offsets int32 [batch + 1]: the prefix sums of ceil(rows of the sample / 256) (n_blocks = the last one);
+ *   planes [n_planes, 6, 4] = (a, b, c, d) of the pasted boxes' faces with the normals pointing inwards (surface_equ_3d,
+ *   mmdet3d/core/bbox/box_np_ops.py:693-714), plane_offsets int32 [batch + 1].  Per row, in this order:
+ *     1. removal (rows at or after n_pasted[s] only): sgn = ((x * a + y * b) + z * c) + d for the six faces of every pasted
+ *        box of the sample; inside iff all six are < 0 (sgn >= 0 is outside, box_np_ops.py:745-751); a row inside any box is
+ *        dropped.  The planes are staged in LDS, sst_augment_plane_chunk() boxes at a time.
+ *     2. flip_h: y = -y; flip_v: x = -x (lidar_box3d.py:195-227).
+ *     3. rotate: x' = x * cos + y * sin, y' = x * (-sin) + y * cos (lidar_box3d.py:166-190, base_points.py:155-177).
+ *     4. x, y, z *= scale.   5. x, y, z += trans.
+ *     6. kept iff x > r0 && y > r1 && z > r2 && x < r3 && y < r4 && z < r5 (base_points.py:223-228): a NaN is dropped.
+ *     7. the other columns are copied; a column k >= 3 named in norm_mask leaves as (v - norm_mean[k]) / norm_std[k], each
+ *        operation in fp32 (NormalizePoints, mmdet3d/datasets/pipelines/loading.py:1026-1050).
+ *   out [n_total, cols]: the survivors packed, sample after sample; counts int32 [batch] (zeroed by the call).  Inside a
+ *   sample: without `shuffle` the input order; with it the order of the STABLE sort by the 32-bit key
+ *     x = seed + 0x9E3779B97F4A7C15 * (((sample << 32) | row) + 1);  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;
+ *     x *= 0x94D049BB133111EB;  x ^= x >> 31;  key = x >> 32       (splitmix64; row = the index inside the sample, 64-bit
+ *   wrap-around arithmetic).  One memset, a classify launch, one sst_sort_pairs_u64 of (dropped | sample | key), a gather
+ *   launch.  Workspace: sst_augment_workspace_bytes(n_total, batch), 16-byte aligned.
+ *
+ * sst_augment_boxes_f32 - boxes [n_boxes, cols] (cols 7 or 9), box_offsets int32 [batch + 1], labels int64 or NULL.  In order:
+ *   flips (flip_h: columns 1 and 8 negated, yaw = -yaw + (float)pi; flip_v: columns 0 and 7, yaw = -yaw; lidar_box3d.py:210-216),
+ *   rotation (centre and columns 7:9 as points, yaw += angle; applied where the record's `rotate` is set or always_rotate),
+ *   scale (columns 0:6 and 7:, base_box3d.py:222-231), translation (0:3); with `filter`: in_range_bev strict on the centre
+ *   (lidar_box3d.py:244-247), the kept rows compacted in their order to boxes_out / labels_out rows box_offsets[s] .., counts
+ *   int32 [batch], and yaw = yaw - floor(yaw / (float)(2 pi) + 0.5f) * (float)(2 pi) (limit_yaw, base_box3d.py:233-245).
+ *   Without `filter` (the seed boxes of the FSD++ loaders) every row is written and the yaw is not limited.  One launch.
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer, a negative size, a misaligned buffer or a workspace
+ * that is too small; SST_ERR_UNSUPPORTED for cols outside the limits or n_total above 2^31 - 257.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_AUG_MAX_COLS 8
+typedef struct sst_augment_params {
+  int32_t flip_h, flip_v, rotate, shuffle;
+  float cos, sin, scale, angle;
+  float trans[3];
+  float reserved;
+  float range[6];
+  uint64_t seed;
+} sst_augment_params;
+typedef struct sst_augment_args {
+  const float* points;
+  const int64_t* row_offsets;
+  const int32_t* n_pasted;
+  const int32_t* block_offsets;
+  const sst_augment_params* params;
+  const float* planes;
+  const int32_t* plane_offsets;
+  float* out;
+  int32_t* counts;
+  void* workspace;
+  int64_t workspace_bytes;
+  int64_t n_total;
+  int32_t batch, cols, n_blocks, n_planes;
+  int32_t norm_mask, reserved;           /* bit k (k >= 3): column k leaves as (v - norm_mean[k]) / norm_std[k] */
+  float norm_mean[SST_AUG_MAX_COLS], norm_std[SST_AUG_MAX_COLS];
+} sst_augment_args;
+typedef struct sst_augment_box_args {
+  const float* boxes;
+  const int64_t* labels;
+  const int32_t* box_offsets;
+  const sst_augment_params* params;
+  float* boxes_out;
+  int64_t* labels_out;
+  int32_t* counts;
+  int32_t batch, cols, n_boxes, filter, always_rotate, reserved;
+} sst_augment_box_args;
+int sst_augment_plane_chunk(void);
+int64_t sst_augment_workspace_bytes(int64_t n_total, int batch);
+int sst_augment_points_f32(const sst_augment_args* args, void* stream);
+int sst_augment_boxes_f32(const sst_augment_box_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,19 @@ IncrDeltaArgs = _struct('IncrDeltaArgs', 'sst_incr_delta_args of include/sst_amd
 FrameTransformArgs = _struct('FrameTransformArgs', 'sst_frame_transform_args of include/sst_amd.h', (
     [('src', ctypes.c_void_p * 8), ('dst', ctypes.c_void_p * 8), ('n', c_i64 * 8), ('mat', (ctypes.c_float * 12) * 8),
      ('n_clouds', _I32), ('cols', _I32)]))
+AugmentParams = _struct('AugmentParams', 'sst_augment_params of include/sst_amd.h', (
+    [(k, _I32) for k in ('flip_h', 'flip_v', 'rotate', 'shuffle')]
+    + [(k, ctypes.c_float) for k in ('cos', 'sin', 'scale', 'angle')]
+    + [('trans', ctypes.c_float * 3), ('reserved', ctypes.c_float), ('range', ctypes.c_float * 6), ('seed', ctypes.c_uint64)]))
+AugmentArgs = _struct('AugmentArgs', 'sst_augment_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('points', 'row_offsets', 'n_pasted', 'block_offsets', 'params', 'planes', 'plane_offsets',
+                                    'out', 'counts', 'workspace')]
+    + [(k, c_i64) for k in ('workspace_bytes', 'n_total')]
+    + [(k, _I32) for k in ('batch', 'cols', 'n_blocks', 'n_planes', 'norm_mask', 'reserved')]
+    + [('norm_mean', ctypes.c_float * 8), ('norm_std', ctypes.c_float * 8)]))
+AugmentBoxArgs = _struct('AugmentBoxArgs', 'sst_augment_box_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('boxes', 'labels', 'box_offsets', 'params', 'boxes_out', 'labels_out', 'counts')]
+    + [(k, _I32) for k in ('batch', 'cols', 'n_boxes', 'filter', 'always_rotate', 'reserved')]))
 FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
@@ -530,6 +543,10 @@ _SIGNATURES = {
     'sst_incr_plan_f32': (c_i32, [c_ptr, c_ptr]),
     'sst_incr_rows_f32': (c_i32, [c_ptr, c_ptr]),
     'sst_points_frame_transform_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_augment_plane_chunk': (c_i32, []),
+    'sst_augment_workspace_bytes': (c_i64, [c_i64, c_i32]),
+    'sst_augment_points_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_augment_boxes_f32': (c_i32, [c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
