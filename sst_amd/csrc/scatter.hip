@@ -227,6 +227,16 @@ __device__ __forceinline__ void seg_block_group_v4(const float* __restrict__ fea
         }
       }
     }
+    if (mode == SST_REDUCE_MAX && beg + part < end && (arg.x == n_rows || arg.y == n_rows || arg.z == n_rows || arg.w == n_rows)) {
+      // a channel that is -inf in every row of the part never won above: it records the part's first (smallest) row, so that
+      // a real row always carries its index into the merge.  Behind the loop: a first-row flag inside it made the launch 5 %
+      // slower (profiles/seg_reduce/edges_before_after.json)
+      const int r0 = (int)perm[beg + part];
+      if (arg.x == n_rows) arg.x = r0;
+      if (arg.y == n_rows) arg.y = r0;
+      if (arg.z == n_rows) arg.z = r0;
+      if (arg.w == n_rows) arg.w = r0;
+    }
     lds_v[threadIdx.x] = acc;
     lds_a[threadIdx.x] = arg;
     __syncthreads();
@@ -237,7 +247,8 @@ __device__ __forceinline__ void seg_block_group_v4(const float* __restrict__ fea
         const float4 v = lds_v[h * L + l];
         const int4 b = lds_a[h * L + l];
         if (mode == SST_REDUCE_MAX) {
-          // a part that saw no point holds (-inf, n_rows): never wins; -inf values of real rows keep the smaller index
+          // a part that saw no point holds (-inf, n_rows): never wins; a part that saw one holds a real row even when every
+          // value is -inf, and equal values keep the smaller index
           if (v.x > r.x || (v.x == r.x && b.x < a.x)) r.x = v.x, a.x = b.x;
           if (v.y > r.y || (v.y == r.y && b.y < a.y)) r.y = v.y, a.y = b.y;
           if (v.z > r.z || (v.z == r.z && b.z < a.z)) r.z = v.z, a.z = b.z;
@@ -288,6 +299,8 @@ __device__ __forceinline__ void seg_block_group_v1(const float* __restrict__ fea
         }
       }
     }
+    // a channel that is -inf in every row of the part never won above: it records the part's first (smallest) row
+    if (mode == SST_REDUCE_MAX && live && arg == n_rows && beg + part < end) arg = (int)perm[beg + part];
     lds_v[threadIdx.x] = acc;
     lds_a[threadIdx.x] = arg;
     __syncthreads();

@@ -244,8 +244,14 @@ class SegmentReduce(Function):
         n, c = feats.shape
         if plan is not None and _long_group_applies(n, m, c, inverse, group_index, m_limit) \
                 and (c % 4 != 0 or feats.data_ptr() % 16 == 0):
-            out = torch.empty((m, c), dtype=torch.float32, device=feats.device)
-            argmax = torch.empty((m, c), dtype=torch.int32, device=feats.device) if mode == 2 else None
+            if getattr(plan, 'native', False):   # unique_rows' own plan: every group has a row, every output row is written
+                out = torch.empty((m, c), dtype=torch.float32, device=feats.device)
+                argmax = torch.empty((m, c), dtype=torch.int32, device=feats.device) if mode == 2 else None
+            else:
+                # a CSR rebuilt from ids (sst_ops.plan_of_inverse) keeps a group for every absent id, and the tile kernel does
+                # not write groups without rows: they read 0 and record the row n, as in every other kernel
+                out = torch.zeros((m, c), dtype=torch.float32, device=feats.device)
+                argmax = torch.full((m, c), n, dtype=torch.int32, device=feats.device) if mode == 2 else None
             scratch = _long_group_scratch(plan, n, m, c, feats.device)
             rc = _lib.load().sst_segment_reduce_long_f32(_lib.ptr(feats), n, c, _lib.ptr(perm), _lib.ptr(inverse),
                                                          int(inverse_shift), _lib.ptr(offsets), m, mode, _lib.ptr(scratch),
