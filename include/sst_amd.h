@@ -2286,6 +2286,55 @@ int64_t sst_augment_workspace_bytes(int64_t n_total, int batch);
 int sst_augment_points_f32(const sst_augment_args* args, void* stream);
 int sst_augment_boxes_f32(const sst_augment_box_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The points of a CTRL tracklet pipeline (csrc/tracklet_augment.hip): TrackletPoseTransform
+ * (mmdet3d/datasets/pipelines/tracklet_pipelines.py:149-208), PointDecoration (:455-506), TrackletRandomFlip (:414-439),
+ * TrackletGlobalRotScaleTrans (:329-355), PointsRangeFilter and PointShuffle for a packed batch of tracklets.  fp32, every
+ * operation rounded on its own (no contraction), integer atomics only, bit-reproducible.
+ *
+ * sst_tracklet_augment_points_f32 - points [n_total, cols] (3 <= cols <= SST_AUG_MAX_COLS, 16-byte aligned), sample after
+ *   sample and inside a sample frame after frame; frame_rows int32 [n_frames + 1]: the first row of every frame of the batch
+ *   (an empty frame repeats its successor's); sample_frames int32 [batch + 1]: the first frame of every sample (at most
+ *   SST_TRK_AUG_MAX_FRAMES frames per sample, max_frames = the largest count); block_offsets int32 [batch + 1]: the prefix sums
+ *   of ceil(rows of the sample / 256) (n_blocks = the last one); frames [n_frames, 12 + deco]: rows 0..2 of the frame's 4 x 4
+ *   matrix m (row-major, 12 values), then the deco (0 <= deco <= SST_TRK_AUG_MAX_DECO) values appended to every row of the
+ *   frame; frame_values int32 [n_frames]: what out_frame_inds holds for a row of the frame; params: one sst_augment_params per
+ *   sample.  Per row, in this order:
+ *     1. its frame: the first frame f of the sample with frame_rows[f + 1] > row (a binary search over the sample's frame
+ *        offsets, staged in LDS).
+ *     2. x' = ((m00 * x + m01 * y) + m02 * z) + m03, y' and z' likewise from rows 1 and 2 of m.
+ *     3. steps 2 to 6 of sst_augment_points_f32 with the sample's record (flips, rotation, scale, translation, the strict range
+ *        test): the same device function.
+ *     4. the other columns are copied; the frame's deco values are appended.
+ *   out [n_total, cols + deco] and out_frame_inds int32 [n_total]: the survivors packed, sample after sample; counts int32
+ *   [batch] (zeroed by the call).  Inside a sample: without `shuffle` the input order, with it the order of the stable sort by
+ *   the key of sst_augment_points_f32 (row = the index inside the sample).  One memset, a classify launch, one
+ *   sst_sort_pairs_u64, a gather launch.  Workspace: sst_tracklet_augment_workspace_bytes(n_total, batch), 16-byte aligned.
+ *   The boxes of the tracklets and their candidates go through sst_augment_boxes_f32 with filter = 0 and always_rotate = 1.
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer, a negative size, a misaligned buffer or a workspace
+ * that is too small; SST_ERR_UNSUPPORTED for cols, deco or max_frames outside the limits or n_total above 2^31 - 257.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_TRK_AUG_MAX_DECO 8
+#define SST_TRK_AUG_MAX_FRAMES 2048
+typedef struct sst_tracklet_augment_args {
+  const float* points;
+  const int32_t* frame_rows;
+  const int32_t* sample_frames;
+  const int32_t* block_offsets;
+  const float* frames;
+  const int32_t* frame_values;
+  const sst_augment_params* params;
+  float* out;
+  int32_t* out_frame_inds;
+  int32_t* counts;
+  void* workspace;
+  int64_t workspace_bytes;
+  int64_t n_total;
+  int32_t batch, cols, deco, n_blocks, n_frames, max_frames;
+} sst_tracklet_augment_args;
+int64_t sst_tracklet_augment_workspace_bytes(int64_t n_total, int batch);
+int sst_tracklet_augment_points_f32(const sst_tracklet_augment_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

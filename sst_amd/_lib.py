@@ -158,6 +158,11 @@ AugmentArgs = _struct('AugmentArgs', 'sst_augment_args of include/sst_amd.h', (
 AugmentBoxArgs = _struct('AugmentBoxArgs', 'sst_augment_box_args of include/sst_amd.h', (
     [(k, ctypes.c_void_p) for k in ('boxes', 'labels', 'box_offsets', 'params', 'boxes_out', 'labels_out', 'counts')]
     + [(k, _I32) for k in ('batch', 'cols', 'n_boxes', 'filter', 'always_rotate', 'reserved')]))
+TrackletAugmentArgs = _struct('TrackletAugmentArgs', 'sst_tracklet_augment_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('points', 'frame_rows', 'sample_frames', 'block_offsets', 'frames', 'frame_values', 'params',
+                                    'out', 'out_frame_inds', 'counts', 'workspace')]
+    + [(k, c_i64) for k in ('workspace_bytes', 'n_total')]
+    + [(k, _I32) for k in ('batch', 'cols', 'deco', 'n_blocks', 'n_frames', 'max_frames')]))
 FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
@@ -547,6 +552,8 @@ _SIGNATURES = {
     'sst_augment_workspace_bytes': (c_i64, [c_i64, c_i32]),
     'sst_augment_points_f32': (c_i32, [c_ptr, c_ptr]),
     'sst_augment_boxes_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_tracklet_augment_workspace_bytes': (c_i64, [c_i64, c_i32]),
+    'sst_tracklet_augment_points_f32': (c_i32, [c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -138,6 +138,19 @@ class LiDARTracklet(object):
         self.dtype = self.boxes.dtype
         self.size = len(self.ts_list)
 
+    def remove(self, ts_list):
+        """drop the frames with these timestamps (lidar_tracklet.py:106-118): ``list_fields`` and ``boxes`` keep the others in
+        their order, the tracklet is frozen again -> keep_idx, the kept frames' former indices"""
+        keep_ts = self.ts_set - set(ts_list if ts_list is not None else [])
+        keep_idx = sorted(self.ts2index[ts] for ts in keep_ts)
+        for f in self.list_fields:
+            if f != 'box_list' and getattr(self, f, None) is not None:
+                attr = getattr(self, f)
+                setattr(self, f, [attr[i] for i in keep_idx])
+        self.boxes = self.boxes[torch.as_tensor(keep_idx, dtype=torch.long, device=self.boxes.device)]
+        self.freeze()
+        return keep_idx
+
     # ---- dump / collate formats ----------------------------------------------------------------------------------------
 
     def to_dump_format(self):
