@@ -2335,6 +2335,105 @@ typedef struct sst_tracklet_augment_args {
 int64_t sst_tracklet_augment_workspace_bytes(int64_t n_total, int batch);
 int sst_tracklet_augment_points_f32(const sst_tracklet_augment_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Test-time augmentation of the CTRL tracklet family (csrc/tracklet_tta.hip).  fp32 with every operation
+ * rounded on its own (no contraction), the merge in fp64; integer atomics only, bit-reproducible.
+ *
+ * sst_tracklet_tta_views_f32 - the n_views views of a packed batch of tracklets in one pass.  Replaces, per view, the deep copy
+ *   and the transforms of MultiScaleFlipAug3D (mmdet3d/datasets/pipelines/test_time_aug.py:88-109): TrackletGlobalRotScaleTrans
+ *   (tracklet_pipelines.py:329-355), TrackletRandomFlip (:414-439), PointsRangeFilter and PointShuffle, behind
+ *   TrackletPoseTransform (:149-208) and PointDecoration (:455-506).  The inputs are those of sst_tracklet_augment_points_f32;
+ *   params holds one sst_augment_params per (view, sample), view-major [n_views * batch].  Per INPUT row, once: its frame (the
+ *   binary search over the LDS-staged offsets), x' = ((m00 x + m01 y) + m02 z) + m03 (y', z' likewise), the copied columns and
+ *   the frame's deco values.  Then per view, in the reference's order: rotation (x' = x cos + y sin, y' = x (-sin) + y cos,
+ *   where `rotate` is set), x, y, z *= scale, += trans, flip_h (y = -y), flip_v (x = -x), the strict range test of
+ *   sst_augment_points_f32.  (sst_augment_points_f32 flips FIRST: its order is not this one.)
+ *   out [n_views * n_total, cols + deco], out_frame_inds int32 [n_views * n_total]: the survivors packed view after view and,
+ *   inside a view, sample after sample; counts int32 [n_views * batch] (zeroed by the call).  Inside a (view, sample): without
+ *   `shuffle` the input order, with it the stable sort by the key of sst_augment_points_f32 with seed + v * 0xD6E8FEB86659FD93
+ *   in place of the seed (view 0 keeps the sample's seed).  One memset, a classify launch, ONE sst_sort_pairs_u64 of
+ *   (dropped | view | sample | key), a gather launch.  Workspace: sst_tracklet_tta_views_workspace_bytes(n_total, batch, n_views,
+ *   cols + deco), 16-byte aligned (0 for sizes the call refuses).
+ * sst_tracklet_tta_boxes_f32 - boxes [n_boxes, cols] (cols 7 or 9), box_offsets int32 [batch + 1] -> boxes_out
+ *   [n_views, n_boxes, cols] in the same order: rotation (centre and columns 7:9, yaw += angle), scale (0:6, 7:), translation
+ *   (0:3), flip_h (columns 1 and 8 negated, yaw = -yaw + (float)pi), flip_v (columns 0 and 7, yaw = -yaw).  One launch.
+ *   sst_augment_boxes_f32 is untouched.
+ * sst_tracklet_tta_finish - what TrackletRoIHead.inverse_aug (mmdet3d/models/roi_heads/tracklet_roi_head.py:168-179),
+ *   LiDARTracklet.update_from_prediction (mmdet3d/core/bbox/structures/lidar_tracklet.py:403-445) and LiDARTracklet.merge_augs
+ *   (:548-602) do, for every tracklet row of the batch in one launch.  boxes [n_views, n_rows, 7], scores [n_views, n_rows],
+ *   valid uint8 [n_views, n_rows]: the decoded boxes of every view; old_boxes [n_rows, 7] (un-augmented, in the shared pose),
+ *   old_scores double [n_rows]; mats [n_rows, 12]: rows 0..2 of inv(pose_i) @ shared_pose; views[k]: flip_h, flip_v, rotate,
+ *   the fp32 angle, its cos and sin.  Per view, fp32: flip_h undone (y = -y, yaw = -yaw + (float)pi), flip_v undone (x = -x,
+ *   yaw = -yaw), rotate(-angle) (x' = x cos + y (-sin), y' = x sin + y cos, yaw += -angle), then the centre by the matrix as
+ *   above and yaw' = atan2(m00 sin yaw + m01 cos yaw, m10 sin yaw + m11 cos yaw); where valid is 0: the old box through the
+ *   matrix and the old score.  Merge in fp64 over k = 0 .. n_views - 1 in this order: MAX - the first view with the largest
+ *   score; WEIGHTED - box[:6] = sum(box_k[:6] * s_k) / sum(s_k), yaw = the median of the fp32 yaws (even n_views: (lower +
+ *   upper) / 2 in fp32), score = sum(s_k) / n_views; IOU_CLAMPED - WEIGHTED with s_k *= (aligned 3-D IoU of view 0's box and
+ *   view k's > iou_merge_thresh ? 1 : 0), the IoU of sst_tracklet_targets_f32, view 0's forced to 1.  0 / 0 follows IEEE.
+ *   merged_boxes double [n_rows, 7], merged_scores double [n_rows]; view_boxes [n_views, n_rows, 7] and view_scores double
+ *   [n_views, n_rows] (the effective scores): both or neither; without them a workspace of
+ *   sst_tracklet_tta_finish_workspace_bytes(n_rows, n_views) bytes, 16-byte aligned, holds them.
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer, a negative size, n_views < 1, a misaligned buffer or a
+ *   workspace that is too small; SST_ERR_UNSUPPORTED for n_views above SST_TRK_TTA_MAX_VIEWS, cols / deco / max_frames outside
+ *   the limits, an unknown merge mode, or more than 2^31 - 257 (view, row) pairs.
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_TRK_TTA_MAX_VIEWS 32
+#define SST_TRK_TTA_MERGE_MAX 0
+#define SST_TRK_TTA_MERGE_WEIGHTED 1
+#define SST_TRK_TTA_MERGE_IOU_CLAMPED 2
+typedef struct sst_tracklet_tta_views_args {
+  const float* points;
+  const int32_t* frame_rows;
+  const int32_t* sample_frames;
+  const int32_t* block_offsets;
+  const float* frames;
+  const int32_t* frame_values;
+  const sst_augment_params* params;       /* [n_views * batch], view-major */
+  float* out;
+  int32_t* out_frame_inds;
+  int32_t* counts;                        /* [n_views * batch] */
+  void* workspace;
+  int64_t workspace_bytes;
+  int64_t n_total;
+  int32_t batch, cols, deco, n_blocks, n_frames, max_frames, n_views, reserved;
+} sst_tracklet_tta_views_args;
+typedef struct sst_tracklet_tta_box_args {
+  const float* boxes;
+  const int32_t* box_offsets;
+  const sst_augment_params* params;       /* [n_views * batch], view-major */
+  float* boxes_out;
+  int32_t batch, cols, n_boxes, n_views;
+} sst_tracklet_tta_box_args;
+typedef struct sst_tracklet_tta_view {
+  int32_t flip_h, flip_v, rotate;
+  float angle, cos, sin;
+  float reserved[2];
+} sst_tracklet_tta_view;
+typedef struct sst_tracklet_tta_finish_args {
+  const float* boxes;
+  const float* scores;
+  const uint8_t* valid;
+  const float* old_boxes;
+  const double* old_scores;
+  const float* mats;
+  double* merged_boxes;
+  double* merged_scores;
+  float* view_boxes;
+  double* view_scores;
+  void* workspace;
+  int64_t workspace_bytes;
+  int64_t n_rows;
+  int32_t n_views, mode;
+  float iou_merge_thresh;
+  int32_t reserved;
+  sst_tracklet_tta_view views[SST_TRK_TTA_MAX_VIEWS];
+} sst_tracklet_tta_finish_args;
+int64_t sst_tracklet_tta_views_workspace_bytes(int64_t n_total, int batch, int n_views, int width);
+int sst_tracklet_tta_views_f32(const sst_tracklet_tta_views_args* args, void* stream);
+int sst_tracklet_tta_boxes_f32(const sst_tracklet_tta_box_args* args, void* stream);
+int64_t sst_tracklet_tta_finish_workspace_bytes(int64_t n_rows, int n_views);
+int sst_tracklet_tta_finish(const sst_tracklet_tta_finish_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,11 +80,14 @@ from . import augment  # noqa: F401
 from .augment import AugmentParams, TrainAugment  # noqa: F401
 from . import tracklet_augment  # noqa: F401
 from .tracklet_augment import TrackletAugment, TrackletParams  # noqa: F401
+from . import tracklet_tta  # noqa: F401
+from .tracklet_tta import TrackletTTA, TrackletTTADetector, attach_tracklet_tta, tta_finish  # noqa: F401
 
 __version__ = '0.1.0'
 
 __all__ = [
     'augment', 'AugmentParams', 'TrainAugment', 'tracklet_augment', 'TrackletAugment', 'TrackletParams',
+    'tracklet_tta', 'TrackletTTA', 'TrackletTTADetector', 'attach_tracklet_tta', 'tta_finish',
     'incremental', 'box_frame_transform_gpu', 'find_delta_points_by_voxelization', 'find_delta_points_by_voxelization_list_v3',
     'generate_points', 'incremental_points_mask', 'points_frame_transform', 'seed_crop', 'fsdpp', 'TwoStageFSDPP',
     'tracklet_detector', 'TimestampEncoder', 'TrackletDetector', 'TrackletPointRoIExtractor', 'TrackletRoIHead', 'TrackletSegmentor',

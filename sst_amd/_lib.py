@@ -163,6 +163,23 @@ TrackletAugmentArgs = _struct('TrackletAugmentArgs', 'sst_tracklet_augment_args 
                                     'out', 'out_frame_inds', 'counts', 'workspace')]
     + [(k, c_i64) for k in ('workspace_bytes', 'n_total')]
     + [(k, _I32) for k in ('batch', 'cols', 'deco', 'n_blocks', 'n_frames', 'max_frames')]))
+TrackletTTAViewsArgs = _struct('TrackletTTAViewsArgs', 'sst_tracklet_tta_views_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('points', 'frame_rows', 'sample_frames', 'block_offsets', 'frames', 'frame_values', 'params',
+                                    'out', 'out_frame_inds', 'counts', 'workspace')]
+    + [(k, c_i64) for k in ('workspace_bytes', 'n_total')]
+    + [(k, _I32) for k in ('batch', 'cols', 'deco', 'n_blocks', 'n_frames', 'max_frames', 'n_views', 'reserved')]))
+TrackletTTABoxArgs = _struct('TrackletTTABoxArgs', 'sst_tracklet_tta_box_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('boxes', 'box_offsets', 'params', 'boxes_out')]
+    + [(k, _I32) for k in ('batch', 'cols', 'n_boxes', 'n_views')]))
+TrackletTTAView = _struct('TrackletTTAView', 'sst_tracklet_tta_view of include/sst_amd.h', (
+    [(k, _I32) for k in ('flip_h', 'flip_v', 'rotate')] + [(k, ctypes.c_float) for k in ('angle', 'cos', 'sin')]
+    + [('reserved', ctypes.c_float * 2)]))
+TrackletTTAFinishArgs = _struct('TrackletTTAFinishArgs', 'sst_tracklet_tta_finish_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('boxes', 'scores', 'valid', 'old_boxes', 'old_scores', 'mats', 'merged_boxes', 'merged_scores',
+                                    'view_boxes', 'view_scores', 'workspace')]
+    + [(k, c_i64) for k in ('workspace_bytes', 'n_rows')]
+    + [(k, _I32) for k in ('n_views', 'mode')] + [('iou_merge_thresh', ctypes.c_float), ('reserved', _I32)]
+    + [('views', TrackletTTAView * 32)]))
 FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
@@ -554,6 +571,11 @@ _SIGNATURES = {
     'sst_augment_boxes_f32': (c_i32, [c_ptr, c_ptr]),
     'sst_tracklet_augment_workspace_bytes': (c_i64, [c_i64, c_i32]),
     'sst_tracklet_augment_points_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_tracklet_tta_views_workspace_bytes': (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    'sst_tracklet_tta_views_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_tracklet_tta_boxes_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_tracklet_tta_finish_workspace_bytes': (c_i64, [c_i64, c_i32]),
+    'sst_tracklet_tta_finish': (c_i32, [c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

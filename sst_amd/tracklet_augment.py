@@ -24,6 +24,7 @@ through ``((m0 x + m1 y) + m2 z) + m3`` in float32 where the reference calls a m
 (the bar: DESIGN.md 3.27).  The tracklets and candidates handed in are modified in place, as the reference's transforms modify
 theirs.  There is no eager fall-back: ``__call__`` needs a GPU."""
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -338,17 +339,12 @@ class TrackletAugment(object):
         return frames, lens
 
     # ------------------------------------------------------------------ the call
-    def __call__(self, points, tracklets, candidates=None, params=None):
-        """points: per sample the list (or object array) of per-frame [n_f, C] float32 arrays or tensors (host or device), or
-        (one concatenated [N, C] array or tensor, the frame lengths); 3 <= C <= 8.  tracklets: one frozen LiDARTracklet per sample
-        with ``pose_list`` set; candidates: per sample the list of its ground-truth candidates (with their own ``pose_list``), or
-        None (test pipelines).  params: a ``TrackletParams`` (default: ``draw_params(tracklets)``).
-
-        -> dict(points: per-sample [n_kept, C + D] VIEWS of the packed output, pts_frame_inds: per-sample int32 views,
-        points_packed, offsets (list, B + 1), counts (list, the one host read of the call), tracklets, candidates: the objects
-        handed in, their ``boxes`` now row ranges of ONE device buffer, ``shared_pose`` set, ``rot_angle`` set on the tracklet as
-        tracklet_pipelines.py:292 sets it; params, records, and per sample pcd_horizontal_flip, pcd_vertical_flip, pcd_rot_angle,
-        pcd_scale_factor, pcd_trans, shared_pose)."""
+    def _stage(self, points, tracklets, candidates, params, records, extra=()):
+        """the host side of a call, shared with sst_amd.tracklet_tta: the checks, ``prepare_boxes``, the tables and ONE packed
+        host-to-device copy of [points | frame offsets | sample tables | frame records | frame values | records | boxes].
+        ``records``: params -> the kernels' records (one per sample here; one per (view, sample) for the test-time views);
+        ``extra``: host arrays that travel in the same copy (their offsets: ``at_extra``).
+        -> a namespace of what the launches need"""
         if not torch.cuda.is_available():
             raise RuntimeError('sst_amd: tensor must be a CUDA/HIP tensor (no CPU path in this library)')
         batch = len(tracklets)
@@ -356,8 +352,6 @@ class TrackletAugment(object):
             raise RuntimeError(f'{WHERE}: one entry of points (and of candidates) per tracklet expected, and at least one tracklet')
         if batch >= 2 ** 31:
             raise NotImplementedError(f'{WHERE}: {batch} samples; the sample field of the sort key holds 2^31 - 1')
-        if params is None:
-            params = self.draw_params(tracklets)
         if len(params) != batch:
             raise RuntimeError(f'{WHERE}: params for {len(params)} samples, {batch} given')
         full_lens = [len(t) for t in tracklets]
@@ -378,7 +372,7 @@ class TrackletAugment(object):
         if max(n_frames) > MAX_FRAMES:
             raise NotImplementedError(f'{WHERE}: a tracklet of {max(n_frames)} frames; the kernels take {MAX_FRAMES} '
                                       f'(SST_TRK_AUG_MAX_FRAMES)')
-        rec = self.records(params)
+        rec = records(params)
 
         # the kept frames of every sample: offsets only, nothing is copied before the packing
         spans, frame_lens = [], []
@@ -445,6 +439,7 @@ class TrackletAugment(object):
         at_fr, at_sf, at_blk = place(frame_rows), place(sample_frames), place(blk_off)
         at_frames, at_fv, at_rec = place(frames), place(frame_values), place(rec)
         at_boxes, at_boff = place(boxes.numpy()), place(box_off)
+        at_extra = [place(e) for e in extra]
         nbytes = cursor[0]
         host = self._buffer('host', nbytes, torch.uint8, None, pin=True)
         host_np = host.numpy()
@@ -480,6 +475,33 @@ class TrackletAugment(object):
         else:
             points_ptr = at(at_points)
 
+        return SimpleNamespace(batch=batch, cols=cols, deco=deco, per_sample=per_sample, boxes=boxes, ranges=ranges, rec=rec,
+                               n_frames=n_frames, n_total=n_total, blk_off=blk_off, total_frames=total_frames, box_cols=box_cols,
+                               dev=dev, stage=stage, at=at, points_ptr=points_ptr, at_fr=at_fr, at_sf=at_sf, at_blk=at_blk,
+                               at_frames=at_frames, at_fv=at_fv, at_rec=at_rec, at_boxes=at_boxes, at_boff=at_boff, at_extra=at_extra)
+
+    def __call__(self, points, tracklets, candidates=None, params=None):
+        """points: per sample the list (or object array) of per-frame [n_f, C] float32 arrays or tensors (host or device), or
+        (one concatenated [N, C] array or tensor, the frame lengths); 3 <= C <= 8.  tracklets: one frozen LiDARTracklet per sample
+        with ``pose_list`` set; candidates: per sample the list of its ground-truth candidates (with their own ``pose_list``), or
+        None (test pipelines).  params: a ``TrackletParams`` (default: ``draw_params(tracklets)``).
+
+        -> dict(points: per-sample [n_kept, C + D] VIEWS of the packed output, pts_frame_inds: per-sample int32 views,
+        points_packed, offsets (list, B + 1), counts (list, the one host read of the call), tracklets, candidates: the objects
+        handed in, their ``boxes`` now row ranges of ONE device buffer, ``shared_pose`` set, ``rot_angle`` set on the tracklet as
+        tracklet_pipelines.py:292 sets it; params, records, and per sample pcd_horizontal_flip, pcd_vertical_flip, pcd_rot_angle,
+        pcd_scale_factor, pcd_trans, shared_pose)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError('sst_amd: tensor must be a CUDA/HIP tensor (no CPU path in this library)')
+        if params is None and len(tracklets) >= 1 and len(points) == len(tracklets) and \
+                (candidates is None or len(candidates) == len(tracklets)):       # otherwise _stage raises before anything is drawn
+            params = self.draw_params(tracklets)
+        st = self._stage(points, tracklets, candidates, params, self.records)
+        batch, cols, deco, per_sample, boxes, ranges, rec = st.batch, st.cols, st.deco, st.per_sample, st.boxes, st.ranges, st.rec
+        n_frames, n_total, blk_off, total_frames, box_cols = st.n_frames, st.n_total, st.blk_off, st.total_frames, st.box_cols
+        dev, at, points_ptr = st.dev, st.at, st.points_ptr
+        at_fr, at_sf, at_blk, at_frames, at_fv, at_rec = st.at_fr, st.at_sf, st.at_blk, st.at_frames, st.at_fv, st.at_rec
+        at_boxes, at_boff = st.at_boxes, st.at_boff
         width = cols + deco
         counts = self._buffer('counts', 2 * batch, torch.int32, dev)
         out = self._buffer('out', (n_total, width), torch.float32, dev)

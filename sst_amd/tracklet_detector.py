@@ -79,12 +79,10 @@ class TrackletPointRoIExtractor(nn.Module):
 
 
 @torch.no_grad()
-def get_bboxes_from_tracklet(rois, cls_score, bbox_pred, valid_roi_mask, class_labels, class_pred, img_metas=None, gt_rois=None,
-                             cfg=None, batch_size=None):
-    """FullySparseBboxHead.get_bboxes_from_tracklet (fsd_bbox_head.py:792-869) over ``roi_decode``: per tracklet (boxes, scores,
-    labels, valid mask), invalid RoIs left in (the tracklet keeps its old box there).  cfg: identical_decode (the RoIs and their
-    scores pass through), replace_center / replace_size / replace_yaw (the ground truth ``gt_rois`` [R, 8] = (valid, box) where
-    it exists).  batch_size: the number of tracklets (default: read from the RoIs, one host read as in the reference)."""
+def decode_tracklet_rows(rois, cls_score, bbox_pred, class_pred, gt_rois=None, cfg=None):
+    """the decoding of FullySparseBboxHead.get_bboxes_from_tracklet (fsd_bbox_head.py:792-869) before it is split by tracklet
+    -> (boxes [R, 7], scores [R]): ``roi_decode``, or the RoIs and their scores under identical_decode; replace_center /
+    replace_size / replace_yaw take the ground truth ``gt_rois`` [R, 8] = (valid, box) where it exists"""
     assert rois.size(0) == cls_score.size(0) == bbox_pred.size(0)
     if _cfg_get(cfg, 'identical_decode', False):
         boxes, scores = rois[:, 1:].clone(), class_pred
@@ -96,6 +94,17 @@ def get_bboxes_from_tracklet(rois, cls_score, bbox_pred, valid_roi_mask, class_l
         if _cfg_get(cfg, key, False):
             assert gt_rois is not None and gt_rois.size(1) == 8
             boxes[:, cols] = torch.where(gt_rois[:, 0:1].bool(), gt_rois[:, gcols].to(boxes.dtype), boxes[:, cols])
+    return boxes, scores
+
+
+@torch.no_grad()
+def get_bboxes_from_tracklet(rois, cls_score, bbox_pred, valid_roi_mask, class_labels, class_pred, img_metas=None, gt_rois=None,
+                             cfg=None, batch_size=None):
+    """FullySparseBboxHead.get_bboxes_from_tracklet (fsd_bbox_head.py:792-869) over ``roi_decode``: per tracklet (boxes, scores,
+    labels, valid mask), invalid RoIs left in (the tracklet keeps its old box there).  cfg: identical_decode (the RoIs and their
+    scores pass through), replace_center / replace_size / replace_yaw (the ground truth ``gt_rois`` [R, 8] = (valid, box) where
+    it exists).  batch_size: the number of tracklets (default: read from the RoIs, one host read as in the reference)."""
+    boxes, scores = decode_tracklet_rows(rois, cls_score, bbox_pred, class_pred, gt_rois, cfg)
     roi_batch_id = rois[..., 0]
     if batch_size is None:
         batch_size = int(roi_batch_id.max().item() + 1)
