@@ -711,14 +711,15 @@ def refuse_fp16(module=None, *tensors, what=None):
                                        'sst_amd._lib.as_fp32), or use the bf16 mode of the encoder stack (set_precision)')
 
 
-def require_cuda(*tensors):
-    """CHECK_INPUT of the reference (scatter_points_cuda.cu:9-15): device + contiguous, else RuntimeError."""
+def require_cuda(*tensors, contiguous=True):
+    """CHECK_INPUT of the reference (scatter_points_cuda.cu:9-15): device + contiguous, else RuntimeError.
+    contiguous=False: the device check alone, for a caller whose kernel takes the strides."""
     for t in tensors:
         if t is None:
             continue
         if not t.is_cuda:
             raise RuntimeError('sst_amd: tensor must be a CUDA/HIP tensor (no CPU path in this library)')
-        if not t.is_contiguous():
+        if contiguous and not t.is_contiguous():
             raise RuntimeError('sst_amd: tensor must be contiguous')
 
 

@@ -106,15 +106,20 @@ class UniquePlan(object):
 def unique_rows(coors, mins=None, extents=None, invalid_if_negative=False, defer_count=False):
     """Sorted-unique of integer rows (torch.unique(dim=0, return_inverse) / at::unique_dim semantics).
 
-    coors: [N, k] int32 or int64 (cuda, contiguous).  mins/extents: per-column lower bound and extent;
+    coors: [N, k] int32 or int64 (cuda, unit inner stride; the rows may be further apart than k, as in a
+    column-sliced view).  mins/extents: per-column lower bound and extent;
     computed from the data (one host sync, like torch.unique itself) when not given.
     invalid_if_negative: 0 = plain lexicographic unique; 1 = rows containing a negative entry form ONE group
     that sorts first; 2 = batched form (column 0 = batch index, see include/sst_amd.h).
     """
-    _lib.require_cuda(coors)
+    _lib.require_cuda(coors, contiguous=False)
     if coors.dtype not in (torch.int32, torch.int64) or coors.dim() != 2:
         raise RuntimeError('sst_amd.unique_rows: coors must be a 2-D int32/int64 tensor')
     n, k = coors.shape
+    if n > 0 and k > 1 and coors.stride(1) != 1:
+        # the row stride travels to the kernel, the inner stride does not: a transposed view would be read as if its
+        # columns were adjacent
+        raise RuntimeError('sst_amd.unique_rows: coors must have unit inner stride')
     dev = coors.device
     lib = _lib.load()
     if n > 0 and (mins is None or extents is None):
@@ -124,6 +129,9 @@ def unique_rows(coors, mins=None, extents=None, invalid_if_negative=False, defer
         mins = [int(v) for v in lohi[0]]
         if int(invalid_if_negative) == 1:
             mins = [max(v, 0) for v in mins]
+        elif int(invalid_if_negative) == 2:
+            # an invalid row is keyed as (b, -1, -1, ...): every column but the first must be able to hold -1
+            mins = mins[:1] + [min(v, -1) for v in mins[1:]]
         extents = [max(int(h) - int(l) + 1, 1) for l, h in zip(mins, lohi[1])]
     elif n == 0:
         mins = [0] * k
