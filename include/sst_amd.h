@@ -2434,6 +2434,61 @@ int sst_tracklet_tta_boxes_f32(const sst_tracklet_tta_box_args* args, void* stre
 int64_t sst_tracklet_tta_finish_workspace_bytes(int64_t n_rows, int n_views);
 int sst_tracklet_tta_finish(const sst_tracklet_tta_finish_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Class-batched cluster assignment (csrc/cluster_classes.hip): ClusterAssigner.forward's per-class loop
+ * (mmdet3d/models/detectors/single_stage_fsd.py:922-999: per class a cluster-voxel grouping of the voted centres, the
+ * occupancy filter with its "nothing survives, so keep every point" rule, the centroids, their connected components and the
+ * point -> component map) for ALL classes of a step in one pass over their concatenated votes, with nothing read back in
+ * between.  The rows of class c are rows class_off[c] .. class_off[c + 1] - 1 of the concatenation.
+ *
+ *   sst_cluster_classes_keys_f32: one launch.  d_rows [n, 5] int32 = (class, sample, cell x, y, z) of every vote, the cell
+ *     being torch.div(p - origin, cell[class], rounding_mode='floor').int() bit for bit.  The caller groups these rows with
+ *     sst_unique_rows over the FIXED key layout of sst_cluster_classes_key_layout (nothing is read back to size the keys) and
+ *     takes the segmented mean of the votes over that grouping.  A sample index outside [0, SST_CCL_MAX_SAMPLES) or a cell
+ *     outside the layout is clamped into it and recorded in d_status (int32 [1], OR-ed: SST_CCL_STATUS_*; the caller zeroes it
+ *     and hands it on to sst_cluster_classes_f32): the result of such a call is not the reference's and must be refused.
+ *   sst_cluster_classes_f32: from that grouping (d_perm, d_offsets, d_inverse, d_num_groups = its device count; the group
+ *     means d_centroids [n, 3], rows >= *d_num_groups unread) to
+ *       d_inds [n, 3] int32   (class, sample, component) of the surviving votes, class after class, inside a class in vote
+ *                             order; the components are numbered from 0 inside every class by their smallest centroid
+ *       d_keep [n] int64      index of every surviving vote INSIDE its class, same order
+ *       d_mask [n] uint8      1 where the vote survives (concatenation order)
+ *       d_sizes [2 * n_classes + 4] int32: surviving votes per class, surviving cluster voxels per class, then the status
+ *                             word, the surviving voxels of all classes, and the 256 x 256 tile pairs of the edge test that
+ *                             were staged and that left early (counted only with count_tiles != 0).
+ *     The edge test is sst_connected_components_xy_f32's (same partition && sqrt(dx*dx + dy*dy) < dist[class], every operation
+ *     rounded on its own); the partition of a centroid is (class, sample) with per_sample, else (class).  A tile pair whose
+ *     partition ranges cannot meet (the centroids are sorted by partition) leaves before it stages anything.
+ *   Integer atomics only (counters, union-find hooks onto the smaller root): bit-reproducible.  Every argument of these entry
+ *   points is checked before the first launch; the three scans in between are called with n >= 1 and carved buffers, the
+ *   only things sst_exclusive_scan_i32 itself refuses.  Workspace: sst_cluster_classes_workspace_bytes(n).
+ * ---------------------------------------------------------------------------------------------- */
+#define SST_CCL_MAX_CLASSES 32
+#define SST_CCL_MAX_SAMPLES 256
+#define SST_CCL_STATUS_CELL_RANGE 1   /* a cluster-voxel coordinate does not fit the fixed key layout */
+#define SST_CCL_STATUS_SAMPLE_RANGE 2 /* a sample index outside [0, SST_CCL_MAX_SAMPLES) */
+typedef struct sst_cluster_classes_params {
+  int32_t n_classes;                           /* 1 .. SST_CCL_MAX_CLASSES */
+  int32_t per_sample;                          /* 1: partition (class, sample) - training; 0: (class) - test */
+  int32_t min_points;
+  int32_t count_tiles;
+  int32_t class_off[SST_CCL_MAX_CLASSES + 1];  /* ascending, class_off[0] = 0, class_off[n_classes] = n */
+  float cell[SST_CCL_MAX_CLASSES][3];          /* cluster voxel size (x, y, z) per class, > 0 */
+  float dist[SST_CCL_MAX_CLASSES];             /* connected_dist per class */
+  float origin[3];
+  int32_t reserved;
+} sst_cluster_classes_params;
+int sst_cluster_classes_max(void);
+/* mins / extents (5 each) of the (class, sample, x, y, z) rows for sst_unique_rows */
+int sst_cluster_classes_key_layout(int n_classes, int64_t* h_mins, int64_t* h_extents);
+int sst_cluster_classes_keys_f32(const float* d_points, int64_t ld, const int32_t* d_batch, int64_t n,
+                                 const sst_cluster_classes_params* params, int32_t* d_rows, int32_t* d_status, void* stream);
+int64_t sst_cluster_classes_workspace_bytes(int64_t n);
+int sst_cluster_classes_f32(const float* d_centroids, const int32_t* d_rows, const uint32_t* d_perm, const int32_t* d_offsets,
+                            const int32_t* d_inverse, const int32_t* d_num_groups, int64_t n,
+                            const sst_cluster_classes_params* params, const int32_t* d_status, int32_t* d_inds, int64_t* d_keep,
+                            uint8_t* d_mask, int32_t* d_sizes, void* d_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

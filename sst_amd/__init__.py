@@ -23,6 +23,7 @@ from .backbones import SIR, SSTv1, SSTv2
 from .cluster import (ClusterAssigner, HybridAssigner, SSGAssigner, connected_components_xy, filter_almost_empty,  # noqa: F401
                       find_connected_componets, find_connected_componets_single_batch, modify_cluster_by_class, ssg,
                       ssg_single_sample)
+from .cluster import cluster_assign_classes, enable_class_batched  # noqa: F401
 from .fps import fps_segmented, furthest_point_sample, furthest_point_sample_with_dist, ssg_assign  # noqa: F401
 from .dynamic_point_pool import DynamicPointROIExtractor, dynamic_point_pool, dynamic_point_pool_mixed
 from . import spconv  # noqa: F401  (sst_amd.spconv mirrors mmdet3d.ops.spconv)
@@ -104,7 +105,7 @@ __all__ = [
     'MODELS', 'VOXEL_ENCODERS', 'MIDDLE_ENCODERS', 'BACKBONES', 'build_voxel_encoder', 'build_middle_encoder',
     'build_backbone', 'WindowPlan', 'sra_attention', 'sra_attention_qk_v', 'ClusterAssigner',
     'find_connected_componets', 'find_connected_componets_single_batch', 'filter_almost_empty',
-    'modify_cluster_by_class', 'connected_components_xy', 'ROI_EXTRACTORS', 'DynamicPointROIExtractor',
+    'modify_cluster_by_class', 'connected_components_xy', 'cluster_assign_classes', 'enable_class_batched', 'ROI_EXTRACTORS', 'DynamicPointROIExtractor',
     'dynamic_point_pool', 'dynamic_point_pool_mixed', 'spconv', 'SparseConvTensor', 'SparseSequential', 'SparseModule',
     'SubMConv3d', 'SparseConv3d', 'SparseConvTranspose3d', 'SparseInverseConv3d', 'SparseMaxPool3d', 'SparseUNet', 'SimpleSparseUNet', 'VirtualVoxelMixer',
     'SparseBasicBlock', 'make_sparse_convmodule',

@@ -42,6 +42,13 @@ class ClusterLossTask(ctypes.Structure):
                 ('d_logits', c_ptr), ('d_reg_preds', c_ptr), ('classes', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class ClusterClassesParams(ctypes.Structure):
+    """sst_cluster_classes_params of include/sst_amd.h"""
+    _fields_ = [('n_classes', ctypes.c_int32), ('per_sample', ctypes.c_int32), ('min_points', ctypes.c_int32),
+                ('count_tiles', ctypes.c_int32), ('class_off', ctypes.c_int32 * 33), ('cell', (ctypes.c_float * 3) * 32),
+                ('dist', ctypes.c_float * 32), ('origin', ctypes.c_float * 3), ('reserved', ctypes.c_int32)]
+
+
 class WgradProblemF32(ctypes.Structure):
     """sst_wgrad_problem_f32 of include/sst_amd.h"""
     _fields_ = [('dy', c_ptr), ('x', c_ptr), ('m', c_i64), ('ld_dy', c_i64), ('ld_x', c_i64), ('dw', c_ptr), ('db', c_ptr),
@@ -576,6 +583,12 @@ _SIGNATURES = {
     'sst_tracklet_tta_boxes_f32': (c_i32, [c_ptr, c_ptr]),
     'sst_tracklet_tta_finish_workspace_bytes': (c_i64, [c_i64, c_i32]),
     'sst_tracklet_tta_finish': (c_i32, [c_ptr, c_ptr]),
+    'sst_cluster_classes_max': (c_i32, []),
+    'sst_cluster_classes_key_layout': (c_i32, [c_i32, c_ptr, c_ptr]),
+    'sst_cluster_classes_keys_f32': (c_i32, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sst_cluster_classes_workspace_bytes': (c_i64, [c_i64]),
+    'sst_cluster_classes_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                        c_ptr, c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

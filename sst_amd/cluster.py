@@ -15,6 +15,8 @@ sampling kernel with ten barriers per sample, three dense matrices ([K, K], [K, 
 nonzero, a sort and one read-back per assert, and in the hybrid assigner a Python loop over the samples.  Here one
 sampling launch and one assignment launch sequence for all samples of a class (csrc/fps.hip), and one read-back.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -110,9 +112,22 @@ class ClusterAssigner(torch.nn.Module):
             return table[self.class_names.index(class_name)]
         return table
 
+    class_batched = False      # opt-in (enable_class_batched): all classes in one pass, one host read (cluster_assign_classes)
+
     @torch.no_grad()
     def forward(self, points_list, batch_idx_list, gt_bboxes_3d=None, gt_labels_3d=None, origin_points=None):
         assert self.num_classes == len(self.class_names)
+        if self.class_batched:
+            # as the zip below: the lists and the names are cut to the shortest of the three
+            names = self.class_names[:min(len(points_list), len(batch_idx_list), len(self.class_names))]
+            g = len(names)
+            if g == 0:                                   # no list or no name: the loop below returns two empty lists
+                return [], []
+            inds3, masks, _ = _assign_classes(
+                list(points_list[:g]), list(batch_idx_list[:g]), [self._per_class(self.cluster_voxel_size, c) for c in names],
+                [self._per_class(self.connected_dist, c) for c in names], self.min_points, self.point_cloud_range[:3],
+                per_sample=self.training)
+            return inds3, masks
         outs = [self.forward_single_class(p, b, c, origin_points)
                 for p, b, c in zip(points_list, batch_idx_list, self.class_names)]
         cluster_inds_list = modify_cluster_by_class([o[0] for o in outs])
@@ -174,6 +189,147 @@ def _nonzero_known(mask, count):
     if hasattr(torch, 'nonzero_static'):
         return torch.nonzero_static(mask, size=int(count)).squeeze(1)
     return torch.nonzero(mask).squeeze(1)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# all classes in one pass (csrc/cluster_classes.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_BATCHED_CLASSES = 32
+MAX_BATCHED_SAMPLES = 256
+
+
+def enable_class_batched(module, on=True):
+    """set ``class_batched`` on every ClusterAssigner below ``module`` (the module itself included): their ``forward`` then
+    clusters all classes in one pass with one host read (``cluster_assign_classes``).  -> the number of assigners found"""
+    found = 0
+    for m in module.modules():
+        if isinstance(m, ClusterAssigner):
+            m.class_batched = bool(on)
+            found += 1
+    return found
+
+
+def _class_tables(n_classes, cell_sizes, dists):
+    cells, ds = [], []
+    if len(cell_sizes) != n_classes or len(dists) != n_classes:
+        raise ValueError(f'sst_amd.cluster_assign_classes: {n_classes} classes, but {len(cell_sizes)} cell sizes and '
+                         f'{len(dists)} distances')
+    for c in range(n_classes):
+        cell = [float(v) for v in cell_sizes[c]]
+        if len(cell) != 3 or not all(v > 0 for v in cell):
+            raise ValueError(f'sst_amd.cluster_assign_classes: cell size of class {c} must be three positive numbers, got {cell}')
+        d = float(dists[c])
+        if d != d:
+            raise ValueError(f'sst_amd.cluster_assign_classes: connected distance of class {c} is not a number')
+        cells.append(cell)
+        ds.append(d)
+    return cells, ds
+
+
+def _assign_classes(points_list, batch_idx_list, cell_sizes, dists, min_points, origin, per_sample, count_tiles=False):
+    """-> ([n_c', 3] int32 (class, sample, component) per class, valid masks with ``_sst_keep`` per class, stats)"""
+    G = len(points_list)
+    if G < 1 or len(batch_idx_list) != G:
+        raise ValueError(f'sst_amd.cluster_assign_classes: {G} point lists and {len(batch_idx_list)} sample-index lists')
+    if G > MAX_BATCHED_CLASSES:
+        raise NotImplementedError(f'sst_amd.cluster_assign_classes: {G} classes; the class-batched pass covers at most '
+                                  f'{MAX_BATCHED_CLASSES}')
+    cells, ds = _class_tables(G, cell_sizes, dists)
+    if len(origin) != 3:
+        raise ValueError('sst_amd.cluster_assign_classes: origin must be (x, y, z)')
+    for c, (p, b) in enumerate(zip(points_list, batch_idx_list)):
+        if not (p.is_cuda and b.is_cuda):
+            raise RuntimeError('sst_amd.cluster_assign_classes: CUDA tensors required (no CPU fallback)')
+        if p.dtype != torch.float32 or p.dim() != 2 or p.size(1) != 3:
+            raise RuntimeError(f'sst_amd.cluster_assign_classes: points of class {c} must be float32 [n, 3]')
+        if b.dim() != 1 or b.size(0) != p.size(0) or b.dtype not in (torch.int32, torch.int64):
+            raise RuntimeError(f'sst_amd.cluster_assign_classes: sample indices of class {c} must be int32 / int64 [n]')
+    dev = points_list[0].device
+    offs = [0]
+    for p in points_list:
+        offs.append(offs[-1] + p.size(0))
+    n = offs[-1]
+    if n >= 1 << 31:
+        raise NotImplementedError('sst_amd.cluster_assign_classes: 2^31 votes or more')
+    stats = dict(host_reads=0, n=n, centroids=0, tiles_run=0, tiles_skipped=0)
+    if n == 0:
+        empty = [(torch.zeros((0, 3), dtype=torch.int32, device=dev), _empty_mask(dev)) for _ in range(G)]
+        return [e[0] for e in empty], [e[1] for e in empty], stats
+    lib = _lib.load()
+    P = _lib.ClusterClassesParams()
+    P.n_classes, P.per_sample, P.min_points, P.count_tiles = G, int(bool(per_sample)), int(min_points), int(bool(count_tiles))
+    for c in range(G + 1):
+        P.class_off[c] = offs[c]
+    for c in range(G):
+        for d in range(3):
+            P.cell[c][d] = cells[c][d]
+        P.dist[c] = ds[c]
+    for d in range(3):
+        P.origin[d] = float(origin[d])
+    pts = torch.cat(points_list, 0) if G > 1 else points_list[0].contiguous()
+    batch = torch.cat([b.int() for b in batch_idx_list], 0) if G > 1 else batch_idx_list[0].int().contiguous()
+    rows = torch.empty((n, 5), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    st = _lib.stream_ptr()
+    _lib.check(lib.sst_cluster_classes_keys_f32(_lib.ptr(pts), pts.stride(0), _lib.ptr(batch), n, ctypes.byref(P), _lib.ptr(rows),
+                                                _lib.ptr(status), st), 'sst_cluster_classes_keys_f32')
+    mins, extents = (ctypes.c_int64 * 5)(), (ctypes.c_int64 * 5)()
+    _lib.check(lib.sst_cluster_classes_key_layout(G, mins, extents), 'sst_cluster_classes_key_layout')
+    # ONE sorted-unique over a key layout that no read-back sizes; its group count stays on the device
+    groups = K.unique_rows(rows, mins=list(mins), extents=list(extents), defer_count=True)
+    # ONE segmented mean: group g -> row g, rows behind the device-side group count are not written (and not read below)
+    every_group = torch.arange(n, dtype=torch.int32, device=dev)
+    centroids = K.segment_reduce(pts, groups, 'mean', group_index=every_group, inverse=groups.inverse, m_limit=groups.num)
+    inds = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    keep = torch.empty(n, dtype=torch.int64, device=dev)
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    sizes = torch.empty(2 * G + 4, dtype=torch.int32, device=dev)
+    ws = _lib.workspace(lib.sst_cluster_classes_workspace_bytes(n), dev)
+    _lib.check(lib.sst_cluster_classes_f32(_lib.ptr(centroids), _lib.ptr(rows), _lib.ptr(groups.perm), _lib.ptr(groups.offsets),
+                                           _lib.ptr(groups.inverse), _lib.ptr(groups.num), n, ctypes.byref(P), _lib.ptr(status),
+                                           _lib.ptr(inds), _lib.ptr(keep), _lib.ptr(mask), _lib.ptr(sizes), _lib.ptr(ws), st),
+               'sst_cluster_classes_f32')
+    sizes = sizes.tolist()                                              # the one read-back of all classes
+    stats.update(host_reads=1, centroids=sizes[2 * G + 1], tiles_run=sizes[2 * G + 2], tiles_skipped=sizes[2 * G + 3])
+    if sizes[2 * G] & 2:
+        raise RuntimeError(f'sst_amd.cluster_assign_classes: a sample index outside [0, {MAX_BATCHED_SAMPLES})')
+    if sizes[2 * G] & 1:
+        raise RuntimeError('sst_amd.cluster_assign_classes: a vote lies further from the origin than the fixed key layout '
+                           'covers (65536 cells in x and y, 16384 in z)')
+    mask = mask.view(torch.bool)
+    inds_list, mask_list, pos = [], [], 0
+    for c in range(G):
+        k = sizes[c]
+        m = mask[offs[c]:offs[c + 1]]
+        m._sst_keep = keep[pos:pos + k]      # the indices of the set entries ride along, as on the per-class path
+        inds_list.append(inds[pos:pos + k])
+        mask_list.append(m)
+        pos += k
+    return inds_list, mask_list, stats
+
+
+def _empty_mask(dev):
+    m = torch.zeros(0, dtype=torch.bool, device=dev)
+    m._sst_keep = torch.zeros(0, dtype=torch.int64, device=dev)
+    return m
+
+
+@torch.no_grad()
+def cluster_assign_classes(points_list, batch_idx_list, cell_sizes, dists, min_points, origin, per_sample):
+    """What the per-class loop of ``ClusterAssigner.forward`` returns before ``modify_cluster_by_class`` - per class
+    ((sample, component) int32 [n', 2], valid mask bool [n] with its index list as ``_sst_keep``) - for up to 32 classes in
+    ONE pass: one key launch over the concatenated votes ((class, sample, cell) with the class's cell size, the cell being
+    ``torch.div(p - origin, cell, rounding_mode='floor').int()`` bit for bit), one sorted-unique, one segmented mean, the
+    occupancy filter with the reference's keep-everything rule decided per class on the device, one connected-components pass
+    over the centroids of all classes (partition (class, sample) with ``per_sample``, else (class): the reference's test path
+    clusters all samples as one graph; ``dists[c]`` per class), and ONE host read (the 2 G sizes).
+
+    ``cell_sizes``: per class (x, y, z); ``dists``: per class.  The centroid of a cluster voxel is the segmented mean of the
+    library over the one grouping; where three or more votes share a voxel its float sum may associate differently from the
+    per-class grouping's (the reduction kernels pick their walk by the shape of the whole call), which can move a centroid by
+    an ulp.  Sums that are exact in fp32, and voxels of one or two votes, give the per-class path's bits."""
+    inds3, masks, _ = _assign_classes(points_list, batch_idx_list, cell_sizes, dists, min_points, origin, per_sample)
+    return [(i[:, 1:], m) for i, m in zip(inds3, masks)]
 
 
 # ----------------------------------------------------------------------------------------------------------------------

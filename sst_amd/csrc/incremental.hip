@@ -14,6 +14,7 @@
 // division (c10::div_floor_floating) operation by operation; the inside test is pib_test.h's, the one sst_points_in_boxes_f32
 // answers with; the transform rounds every product and sum on its own in the order the header states.
 #include "common.h"
+#include "floor_div.h"
 #include "pib_test.h"
 
 namespace {
@@ -22,22 +23,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxBins = SST_INCR_MAX_FRAMES + SST_INCR_MAX_QUERIES;
 constexpr int kMaxW = SST_INCR_MAX_COLS + 1;
-
-// torch.div(p - lo, vs, rounding_mode='floor').int() of one fp32 element (vs > 0)
-__device__ __forceinline__ int32_t floor_div_coor(float p, float lo, float vs) {
-  const float a = __fsub_rn(p, lo);
-  const float mod = fmodf(a, vs);
-  float div = __fdiv_rn(__fsub_rn(a, mod), vs);
-  if (mod != 0.f && ((vs < 0.f) != (mod < 0.f))) div = __fsub_rn(div, 1.f);
-  float fd;
-  if (div != 0.f) {
-    fd = floorf(div);
-    if (__fsub_rn(div, fd) > 0.5f) fd = __fadd_rn(fd, 1.f);
-  } else {
-    fd = copysignf(0.f, __fdiv_rn(a, vs));
-  }
-  return (int32_t)fd;
-}
 
 struct Grid3 {
   int32_t x, y, z;

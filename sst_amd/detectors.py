@@ -24,6 +24,7 @@ Reference:
 import torch
 from torch import nn
 
+from . import fg_group_sample as GS
 from . import fg_sample as FS
 from . import kernels as K
 from . import seg_loss
@@ -665,7 +666,7 @@ class SingleStageFSD(_HotPathDetector):
         gathers them once, after the cluster filter, from ``source`` (the input dictionary, which rides along).  One host read.
         The reference's ``assert (seg_logits < 0).any()`` - a device read for a debugging check - is dropped."""
         if _get(self.cfg, 'group_sample', False):
-            raise NotImplementedError('SingleStageFSD.sample: group_sample (the softmax score path) is not built')
+            return self.group_sample(dict_to_sample, offset, gt_bboxes_3d, gt_labels_3d, batch_size)
         seg_logits = dict_to_sample['seg_logits']
         if seg_logits.size(1) != self.num_classes:
             raise NotImplementedError('SingleStageFSD.sample: seg_logits with a background column (the softmax score path, '
@@ -675,6 +676,66 @@ class SingleStageFSD(_HotPathDetector):
         out = dict(FS.fg_sample(seg_logits, offset, seg_points, batch_idx, thr, self._num_samples(batch_idx, batch_size), extra))
         out['source'] = dict_to_sample
         return out
+
+    # the softmax score path (single_stage_fsd.py:818-919) over csrc/fg_group_sample.hip: a "class" downstream is a GROUP
+    def _groups(self):
+        """the groups of ``cfg.group_names`` as lists of class indices, after the refusals by name"""
+        cfg = self.train_cfg if self.training else self.test_cfg
+        if _get(self.cfg, 'offset_weight', 'max') != 'max':
+            raise NotImplementedError(f"SingleStageFSD.get_offset_weight: offset_weight {self.cfg['offset_weight']!r} (only 'max', "
+                                      'as in the reference)')
+        if _get(cfg, 'add_gt_fg_points', False):
+            raise NotImplementedError('SingleStageFSD.group_sample: add_gt_fg_points with group_sample (the reference passes no '
+                                      'boxes to get_fg_mask there and cannot run it)')
+        if _get(self.cfg, 'group_names', None) is None or _get(self.cfg, 'class_names', None) is None:
+            raise NotImplementedError('SingleStageFSD.group_sample: the config sets group_sample without group_names / class_names')
+        groups = GS.groups_by_names(self.cfg['group_names'], self.cfg['class_names'])
+        if len(groups) != len(self.cfg['score_thresh']):
+            raise RuntimeError(f"SingleStageFSD.group_sample: {len(groups)} groups for {len(self.cfg['score_thresh'])} score thresholds")
+        return GS.check_groups(groups, self.num_classes + 1)
+
+    def group_sample(self, dict_to_sample, offset, gt_bboxes_3d=None, gt_labels_3d=None, batch_size=None):
+        """single_stage_fsd.py:818-881 over ``fg_group_sample.group_sample``: fp32 softmax over ``num_classes + 1`` logits, the
+        scores summed per group (background excluded), ``score_thresh`` per group (+ ``threshold_buffer``), the at-least-one-point
+        rule per (group, sample), the centre ``point + sum_k w_k offset_k`` with the ``'max'`` weights.  -> per-GROUP lists in the
+        layout of ``sample``; ``disable_pretrain`` takes ``disable_pretrain_topks`` with one entry per group.  One host read."""
+        seg_logits = dict_to_sample['seg_logits']
+        groups = self._groups()
+        if seg_logits.size(1) != self.num_classes + 1:
+            raise NotImplementedError(f'SingleStageFSD.group_sample: seg_logits must have num_classes + 1 = {self.num_classes + 1} '
+                                      f'columns (the background last), got {seg_logits.size(1)}')
+        seg_points, batch_idx = dict_to_sample['seg_points'], dict_to_sample['batch_idx']
+        if self.training and _get(self.train_cfg, 'disable_pretrain', False) and not self.runtime_info.get('enable_detection', False):
+            topks = list(_get(self.train_cfg, 'disable_pretrain_topks', [100, 100, 100]))
+            if len(topks) != len(groups):
+                raise NotImplementedError(f'SingleStageFSD.group_sample: disable_pretrain_topks has {len(topks)} entries for '
+                                          f'{len(groups)} groups')
+            thr, extra = [float('inf')] * len(groups), GS.group_topk_extra_mask(seg_logits, groups, topks)
+        else:
+            buffer_thr = self.runtime_info.get('threshold_buffer', 0) if (self.training and self.runtime_info is not None) else 0
+            thr, extra = FS.round_thresholds(list(self.cfg['score_thresh']), buffer_thr), None
+        out = dict(GS.group_sample(seg_logits, offset, seg_points, batch_idx, groups, thr, self._num_samples(batch_idx, batch_size),
+                                   1, extra))
+        out['source'] = dict_to_sample
+        return out
+
+    def gather_group_by_names(self, scores):
+        """single_stage_fsd.py:907-919: [N, num_classes] scores -> [N, G], the columns of every group summed"""
+        groups = GS.groups_by_names(self.cfg['group_names'], self.cfg['class_names'])
+        return torch.stack([scores[:, g].sum(1) for g in groups], dim=1)
+
+    def gather_group(self, scores, group_lens):
+        """single_stage_fsd.py:893-905: consecutive column runs of the given lengths summed"""
+        assert sum(group_lens) == scores.size(1)
+        return torch.stack([s.sum(1) for s in torch.split(scores, list(group_lens), dim=1)], dim=1)
+
+    def get_offset_weight(self, seg_logit):
+        """single_stage_fsd.py:883-891: 1 on the maxima of a row (within 1e-6), shared among equal maxima"""
+        if _get(self.cfg, 'offset_weight', 'max') != 'max':
+            raise NotImplementedError(f"SingleStageFSD.get_offset_weight: offset_weight {self.cfg['offset_weight']!r} (only 'max', "
+                                      'as in the reference)')
+        weight = ((seg_logit - seg_logit.max(1)[0][:, None]).abs() < 1e-6).float()
+        return weight / weight.sum(1)[:, None]
 
     def update_sample_results_by_mask(self, sampled_out, valid_mask_list):
         """single_stage_fsd.py:571-586 over ``fg_gather_cat``: the narrow per-class lists are indexed by the assigner's
