@@ -2489,6 +2489,86 @@ int sst_cluster_classes_f32(const float* d_centroids, const int32_t* d_rows, con
                             const sst_cluster_classes_params* params, const int32_t* d_status, int32_t* d_inds, int64_t* d_keep,
                             uint8_t* d_mask, int32_t* d_sizes, void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CTRL's offline stage (csrc/tracklet_prep.hip): the compute loops of the reference's tools/ctrl/ scripts, each
+ * for a whole batch in one launch.  fp32 data, int64 timestamps, integer atomics only, no order that depends on scheduling: two
+ * runs are bit-equal.
+ *
+ * sst_tracklet_affinity_f32 - replaces the pair loop of tools/ctrl/generate_candidates.py:39-66 (tracklet_assign: per predicted
+ *   tracklet a Python loop over the ground-truth tracklets of its segment) with LiDARTracklet.max_iou
+ *   (mmdet3d/core/bbox/structures/lidar_tracklet.py:210-229: a set intersection, two cats, two .cuda() copies, one
+ *   aligned_iou_3d launch and one .item() per pair).  One wave per pair, sst_tracklet_affinity_pairs_per_block() pairs of one
+ *   predicted tracklet per workgroup.
+ *   Inputs: pd_boxes [n_pd_rows, 7] and pd_ts int64 [n_pd_rows] (ascending within a tracklet) of the predicted tracklets with
+ *   pd_offsets int64 [n_pd + 1]; gt_boxes / gt_ts / gt_offsets [n_gt + 1] likewise; pd_gt_begin / pd_gt_end int64 [n_pd]: the
+ *   half-open range of ground-truth tracklets predicted tracklet p is paired with (its own segment's: the tracklets are sorted
+ *   by segment on the host); out_offsets int64 [n_pd + 1]: the offset of p's row in the ragged output (out_offsets[p + 1] -
+ *   out_offsets[p] >= its range); block_offsets int64 [n_pd + 1]: the cumulative number of workgroups, ceil(range /
+ *   pairs_per_block) per predicted tracklet; n_blocks = block_offsets[n_pd].  Offsets and ranges are clamped to their arrays.
+ *   Output: affinity [n_out] fp32, affinity[out_offsets[p] + (g - pd_gt_begin[p])] = the maximum over the shared timestamps of
+ *   LiDARInstance3DBoxes.aligned_iou_3d(pd box, gt box) (lidar_box3d.py:404-450, the value of sst_tracklet_targets_f32 bit for
+ *   bit; a NaN wins the maximum, as in torch.max), 0 without a shared timestamp.  Elements outside every range are not written.
+ *
+ * sst_box_crops_count_f32 / sst_box_crops_fill_f32 - replace the per-box loop of tools/ctrl/generate_track_input.py:88-101
+ *   (extract_and_save_point: per frame and box one points_in_boxes launch chain on the whole cloud, a boolean mask, an index
+ *   and a copy to the host) and, with the count alone, tools/ctrl/remove_empty.py:82-134 (process_single_frame /
+ *   get_grouping_mask with group_size = 1: "does this box hold a point").  A batch of n_frames frames: points [n_points, cols]
+ *   (cols >= 3, xyz first) frame after frame with pt_offsets int64 [n_frames + 1]; boxes [n_boxes, 7] ([x, y, z_bottom, w, l, h,
+ *   ry], already modified by the caller) with box_offsets int64 [n_frames + 1].  Every box is tested alone against every point
+ *   of its frame with the inside test of csrc/pib_test.h (dpp_box(roi, 0, 0, 0), dpp_classify == 1: sst_points_in_boxes_f32's).
+ *   A workgroup takes a tile of sst_box_crops_tile() consecutive points of one frame: tile_offsets int64 [n_frames + 1] = the
+ *   cumulative number of tiles, ceil(N_f / tile) per frame (n_tiles = its last element); cell_offsets int64 [n_frames + 1] =
+ *   the cumulative B_f * T_f (n_cells = its last element): cell (f, b, t) = cell_offsets[f] + b * T_f + t.
+ *   count: counts int32 [n_boxes] = points inside every box (zeroed here; integer atomics over the tiles).  With tile_counts
+ *     (int32 [n_cells]) also the per-cell counts, their exclusive scan tile_starts (int32 [n_cells], sst_exclusive_scan_i32) and
+ *     total int32 [1] - the one value the caller reads to size the fill; workspace: sst_box_crops_workspace_bytes(n_cells).
+ *     With tile_counts == NULL: the count-only entry, one launch.
+ *   fill: rows [n_rows, cols] = the points inside, in (frame, box, ascending point index) order - the order
+ *     pc[inbox_inds == 0] gives the reference - and src int64 [n_rows] = the point's index in its frame.  Only cells with a
+ *     non-zero count are tested again; a row's slot is tile_starts[cell] + its ballot rank.  Rows of any width are copied
+ *     float by float (24-byte rows are not 16-byte aligned).
+ * Errors (nothing is launched): SST_ERR_ARG for a NULL required pointer, a negative size or cols < 3; SST_ERR_UNSUPPORTED for
+ * sizes above 2^31 - 1.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sst_tracklet_affinity_args {
+  const float* pd_boxes;
+  const int64_t* pd_ts;
+  const int64_t* pd_offsets;
+  const float* gt_boxes;
+  const int64_t* gt_ts;
+  const int64_t* gt_offsets;
+  const int64_t* pd_gt_begin;
+  const int64_t* pd_gt_end;
+  const int64_t* out_offsets;
+  const int64_t* block_offsets;
+  float* affinity;
+  int64_t n_pd_rows, n_gt_rows, n_pd, n_gt, n_out, n_blocks;
+} sst_tracklet_affinity_args;
+typedef struct sst_box_crops_args {
+  const float* points;
+  const float* boxes;
+  const int64_t* pt_offsets;
+  const int64_t* box_offsets;
+  const int64_t* tile_offsets;
+  const int64_t* cell_offsets;
+  int32_t* counts;
+  int32_t* tile_counts;
+  int32_t* tile_starts;
+  int32_t* total;
+  float* rows;
+  int64_t* src;
+  void* workspace;
+  int64_t workspace_bytes, n_points, n_boxes, n_tiles, n_cells, n_rows;
+  int32_t n_frames, cols;
+} sst_box_crops_args;
+int sst_tracklet_affinity_pairs_per_block(void);
+int sst_tracklet_affinity_f32(const sst_tracklet_affinity_args* args, void* stream);
+int sst_box_crops_tile(void);
+int sst_box_crops_box_chunk(void);   /* boxes staged in LDS at a time by the count kernel */
+int64_t sst_box_crops_workspace_bytes(int64_t n_cells);
+int sst_box_crops_count_f32(const sst_box_crops_args* args, void* stream);
+int sst_box_crops_fill_f32(const sst_box_crops_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,10 +83,15 @@ from . import tracklet_augment  # noqa: F401
 from .tracklet_augment import TrackletAugment, TrackletParams  # noqa: F401
 from . import tracklet_tta  # noqa: F401
 from .tracklet_tta import TrackletTTA, TrackletTTADetector, attach_tracklet_tta, tta_finish  # noqa: F401
+from . import tracklet_prep  # noqa: F401
+from .tracklet_prep import (box_point_counts, box_point_crops, candidate_stats, crop_tracklet_points,  # noqa: F401
+                            generate_candidates, remove_empty_boxes, tracklet_affinity)
 
 __version__ = '0.1.0'
 
 __all__ = [
+    'tracklet_prep', 'tracklet_affinity', 'generate_candidates', 'candidate_stats', 'box_point_crops', 'box_point_counts',
+    'crop_tracklet_points', 'remove_empty_boxes',
     'augment', 'AugmentParams', 'TrainAugment', 'tracklet_augment', 'TrackletAugment', 'TrackletParams',
     'tracklet_tta', 'TrackletTTA', 'TrackletTTADetector', 'attach_tracklet_tta', 'tta_finish',
     'incremental', 'box_frame_transform_gpu', 'find_delta_points_by_voxelization', 'find_delta_points_by_voxelization_list_v3',

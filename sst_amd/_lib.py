@@ -187,6 +187,15 @@ TrackletTTAFinishArgs = _struct('TrackletTTAFinishArgs', 'sst_tracklet_tta_finis
     + [(k, c_i64) for k in ('workspace_bytes', 'n_rows')]
     + [(k, _I32) for k in ('n_views', 'mode')] + [('iou_merge_thresh', ctypes.c_float), ('reserved', _I32)]
     + [('views', TrackletTTAView * 32)]))
+TrackletAffinityArgs = _struct('TrackletAffinityArgs', 'sst_tracklet_affinity_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('pd_boxes', 'pd_ts', 'pd_offsets', 'gt_boxes', 'gt_ts', 'gt_offsets', 'pd_gt_begin', 'pd_gt_end',
+                                    'out_offsets', 'block_offsets', 'affinity')]
+    + [(k, c_i64) for k in ('n_pd_rows', 'n_gt_rows', 'n_pd', 'n_gt', 'n_out', 'n_blocks')]))
+BoxCropsArgs = _struct('BoxCropsArgs', 'sst_box_crops_args of include/sst_amd.h', (
+    [(k, ctypes.c_void_p) for k in ('points', 'boxes', 'pt_offsets', 'box_offsets', 'tile_offsets', 'cell_offsets', 'counts',
+                                    'tile_counts', 'tile_starts', 'total', 'rows', 'src', 'workspace')]
+    + [(k, c_i64) for k in ('workspace_bytes', 'n_points', 'n_boxes', 'n_tiles', 'n_cells', 'n_rows')]
+    + [(k, _I32) for k in ('n_frames', 'cols')]))
 FgGroupOffsets = _struct('FgGroupOffsets', 'sst_fg_group_offsets of include/sst_amd.h', [('off', c_i64 * 33)])
 
 _P = ctypes.c_void_p
@@ -589,6 +598,13 @@ _SIGNATURES = {
     'sst_cluster_classes_workspace_bytes': (c_i64, [c_i64]),
     'sst_cluster_classes_f32': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                         c_ptr, c_ptr, c_ptr]),
+    'sst_tracklet_affinity_pairs_per_block': (c_i32, []),
+    'sst_tracklet_affinity_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_box_crops_tile': (c_i32, []),
+    'sst_box_crops_box_chunk': (c_i32, []),
+    'sst_box_crops_workspace_bytes': (c_i64, [c_i64]),
+    'sst_box_crops_count_f32': (c_i32, [c_ptr, c_ptr]),
+    'sst_box_crops_fill_f32': (c_i32, [c_ptr, c_ptr]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

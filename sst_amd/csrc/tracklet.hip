@@ -14,6 +14,7 @@
 // roi_target_row, the RoI head's own.
 #include "common.h"
 #include "roi_target.h"
+#include "tracklet_ts.h"
 
 namespace {
 
@@ -24,17 +25,6 @@ constexpr int kMaxCls = SST_ROI_MAX_CLASSES;
 // ------------------------------------------------------------------------------------------------------------------
 // targets: one workgroup per tracklet
 // ------------------------------------------------------------------------------------------------------------------
-
-// position of t in the ascending list ts[0 .. n), -1 if absent
-__device__ __forceinline__ int find_ts(const int64_t* __restrict__ ts, int n, int64_t t) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (ts[mid] < t) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < n && ts[lo] == t ? lo : -1;
-}
 
 // integer sum over the workgroup (order does not matter); every thread must call
 __device__ __forceinline__ int block_count(int v, int* wcnt) {

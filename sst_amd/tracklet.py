@@ -197,6 +197,31 @@ class LiDARTracklet(object):
         inter = self.ts_set.intersection(trk.ts_set)
         return sorted(list(inter)) if return_sorted else inter
 
+    def ts_iou(self, trk_b):
+        """the share of the two tracklets' timestamps that both have (lidar_tracklet.py:202-208)"""
+        sa, sb = set(self.ts_list), set(trk_b.ts_list)
+        union = len(sa.union(sb))
+        assert union > 0
+        return len(sa.intersection(sb)) / union
+
+    def max_iou(self, trk):
+        """the largest aligned_iou_3d over the shared timestamps, 0 without one (lidar_tracklet.py:210-229) -> a Python float:
+        the affinity kernel of sst_amd.tracklet_prep on this one pair (tracklet_affinity runs it on every pair of a segment)"""
+        assert self.in_world == trk.in_world
+        from . import tracklet_prep
+        dev = tracklet_prep._device(None, [self.boxes, trk.boxes])
+        return float(tracklet_prep._affinity_launch([self], [trk], [(0, 1)], dev)[0].item())
+
+    def append_pc(self, pc, ts=None):
+        """lidar_tracklet.py:70-74: the points of the next frame, in the order of ts_list"""
+        assert self.frozen
+        if ts is not None:
+            assert ts == self.ts_list[len(self.pc_list)]
+        self.pc_list.append(pc)
+
+    def free_pc(self):
+        self.pc_list = None
+
     def get_index_from_ts(self, ts):
         assert self.frozen
         return self.ts2index.get(ts, -1)
