@@ -37,6 +37,7 @@
 
 #include "common.h"
 #include "mfma_tile.h"   // split2 and mma32 of sp_wgrad_os_x6_k (the other kernels here run the fp32 instruction)
+#include "spconv_os_wgrad.h"   // kWgStage, os_find_chunk, os_wg_unit: shared with sp_wgrad_os_bf16_k
 
 namespace {
 
@@ -338,23 +339,7 @@ __global__ __launch_bounds__(256) void sp_os_tile_work_k(const int32_t* __restri
 //   * partial blocks per chunk are summed in chunk order by sp_wgrad_os_reduce_k (deterministic): 4 x fewer, larger chunks.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kWgChunk = 2048;  // pairs per workgroup (upper bound; os_wgrad_chunk_size picks 512 .. 2048)
-constexpr int kWgStage = 64;    // pairs per stage
 constexpr int kWgLd = 68;       // LDS row stride (floats) of a [64 channels][64 pairs] image
-
-__device__ __forceinline__ bool os_find_chunk(const int32_t* __restrict__ num, int kvol, int chunk, int csize, int& k,
-                                              int& first) {
-  int c0 = 0;
-  for (int i = 0; i < kvol; ++i) {
-    const int nc = (num[i] + csize - 1) / csize;
-    if (chunk < c0 + nc) {
-      k = i;
-      first = c0;
-      return true;
-    }
-    c0 += nc;
-  }
-  return false;
-}
 
 __global__ __launch_bounds__(256) void sp_wgrad_os_k(const float* __restrict__ x, int64_t ldx,
                                                      const float* __restrict__ dy, int64_t lddy,
@@ -493,12 +478,9 @@ __global__ __launch_bounds__(256) void sp_wgrad_os_reduce_k(const float* __restr
 // rows global -> registers -> LDS transposed, indices two stages ahead), different LDS image: per operand three bf16 images
 // [64 channels][64 pairs] of 128-byte rows, written as 8-byte groups of 4 consecutive pairs (a thread stages 4 consecutive
 // pairs x 4 channels: its split yields the three parts of 4 pairs per channel), read as the 16-byte fragments the
-// instruction wants (lane (l15, g): 8 consecutive pairs 32 ks + 8 g .. of channel row l15).  16-byte unit G of row r sits at
-// G ^ f(r), f(r) = ((r >> 1) & 7) ^ ((r >> 3) & 7): the sixteen rows of a fragment read cover all 64 banks once, the sixteen
-// channel blocks of a write land two per 8-byte slot.  One buffer (48 KB, three workgroups per CU): the stage in registers
-// waits for a barrier behind the products of the stage in LDS.
-__device__ __forceinline__ int wx6_unit(int row, int G) { return (G ^ ((row >> 1) & 7) ^ ((row >> 3) & 7)) & 7; }
-
+// instruction wants (lane (l15, g): 8 consecutive pairs 32 ks + 8 g .. of channel row l15), swizzled by os_wg_unit
+// (csrc/spconv_os_wgrad.h).  One buffer (48 KB, three workgroups per CU): the stage in registers waits for a barrier behind the
+// products of the stage in LDS.
 __global__ __launch_bounds__(256) void sp_wgrad_os_x6_k(const float* __restrict__ x, int64_t ldx,
                                                         const float* __restrict__ dy, int64_t lddy,
                                                         const int32_t* __restrict__ pairs, int64_t pair_ld, int x_side,
@@ -545,7 +527,7 @@ __global__ __launch_bounds__(256) void sp_wgrad_os_x6_k(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int row = 4 * ch4 + e;
-      const int off = row * 128 + wx6_unit(row, pq >> 1) * 16 + (pq & 1) * 8;
+      const int off = row * 128 + os_wg_unit(row, pq >> 1) * 16 + (pq & 1) * 8;
       unsigned a0[2], a1[2], a2[2], b0[2], b1[2], b2[2];
       split2(live[0] ? ra[0][e] : 0.f, live[1] ? ra[1][e] : 0.f, a0[0], a1[0], a2[0]);
       split2(live[2] ? ra[2][e] : 0.f, live[3] ? ra[3][e] : 0.f, a0[1], a1[1], a2[1]);
@@ -580,7 +562,7 @@ __global__ __launch_bounds__(256) void sp_wgrad_os_x6_k(const float* __restrict_
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int ra_ = wi + 16 * h + l15, rb_ = wj + 16 * h + l15;
-        const int oa = ra_ * 128 + wx6_unit(ra_, 4 * ks + g) * 16, ob = rb_ * 128 + wx6_unit(rb_, 4 * ks + g) * 16;
+        const int oa = ra_ * 128 + os_wg_unit(ra_, 4 * ks + g) * 16, ob = rb_ * 128 + os_wg_unit(rb_, 4 * ks + g) * 16;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           af[h][q] = *(const u32x4*)(img[q] + oa);
