@@ -776,6 +776,7 @@ typedef struct sst_encoder_layer_fwd_args {
                     with w_out = w1 = w2 = NULL: already formed by sst_encoder_tail_pack_f32x6_many, only read */
   const float* xpos_table;     /* with xp == NULL: x + pos is formed on load from the positional table [P][128] ... */
   const int32_t* xpos_idx;     /* ... and the table row of every token (int32 [m]); then pos_table / y2p are normally NULL */
+  int32_t tail_flags;          /* the `flags` of the tail kernel (SST_TAIL_HANDOVER: s1, pre, s2 are hand-over buffers); same in both calls */
 } sst_encoder_layer_fwd_args;
 typedef struct sst_encoder_layer_bwd_args {
   int64_t m, n_windows;
@@ -794,6 +795,7 @@ typedef struct sst_encoder_layer_bwd_args {
   const void* wpack;
   const float* xpos_table;     /* with xp == NULL (as in the forward call): the weight gradient of W_q | W_k reads x + table rows */
   const int32_t* xpos_idx;
+  int32_t tail_flags;          /* as in the forward call */
 } sst_encoder_layer_bwd_args;
 int64_t sst_encoder_layer_bwd_workspace_bytes(int64_t m, int n_heads);
 int64_t sst_encoder_layer_wpack_bytes(void);
@@ -816,10 +818,16 @@ int sst_encoder_layer_bwd_f32x6(const sst_encoder_layer_bwd_args* args, void* st
  *             dn2w | dn2b | dn1w | dn1b [128] = the LayerNorm parameter gradients (m == 0: zeros).  workspace:
  *             sst_encoder_tail_bwd_workspace_bytes(m), 256-byte aligned.
  * The weight gradients of the three linears are the caller's (sst_weight_grad_group_f32x6 on (ds2, h), (dpre, y1), (ds1, o)).
+ *   flags   : 0 = all tensors row-major, as described above.  SST_TAIL_HANDOVER (the same value in the forward and the
+ *             backward call): s1, s2 and pre are a private hand-over between the two kernels.  Each is a buffer of
+ *             sst_encoder_tail_handover_rows(m) rows (x 128 / 256 floats) in a tile-blocked layout nobody else should read
+ *             (csrc/layer_tail_x6.hip; sst_amd/dense.py handover_to_rows undoes it for tests), and `pre` holds act'(pre), the
+ *             derivative the backward kernel multiplies by.  Every other tensor, and every result, is what it is with flags 0.
  * ---------------------------------------------------------------------------------------------- */
+#define SST_TAIL_HANDOVER 1
 typedef struct sst_encoder_tail_fwd_args {
   int64_t m;
-  int32_t act, reserved;
+  int32_t act, flags;
   float eps, reserved_f;
   const float *o, *x;
   const void* packed;
@@ -830,7 +838,7 @@ typedef struct sst_encoder_tail_fwd_args {
 } sst_encoder_tail_fwd_args;
 typedef struct sst_encoder_tail_bwd_args {
   int64_t m;
-  int32_t act, reserved;
+  int32_t act, flags;
   const float *dy2, *dy2p, *s2, *st2, *pre, *s1, *st1;
   const void* packed;
   const float *n1w, *n2w;
@@ -838,6 +846,7 @@ typedef struct sst_encoder_tail_bwd_args {
   float *dn2w, *dn2b, *dn1w, *dn1b;
   void* workspace;
 } sst_encoder_tail_bwd_args;
+int64_t sst_encoder_tail_handover_rows(int64_t m);   /* m rounded up to the rows of a workgroup; m < 0: SST_ERR_ARG */
 int64_t sst_encoder_tail_pack_bytes(void);
 int sst_encoder_tail_pack_f32x6(const float* d_w_out, const float* d_w1, const float* d_w2, void* d_packed, void* stream);
 /* the images of n layers in ONE launch (arrays of n device pointers in HOST memory; d_packed[i]: sst_encoder_tail_pack_bytes()

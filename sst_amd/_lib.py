@@ -205,7 +205,7 @@ EncoderLayerFwdArgs = _struct('EncoderLayerFwdArgs', 'sst_encoder_layer_fwd_args
     + [(k, _P) for k in ('x', 'xp', 'w_in', 'b_in', 'w_out', 'b_out', 'w1', 'b1', 'w2', 'b2', 'n1w', 'n1b', 'n2w', 'n2b',
                          'tok', 'winoff', 'order', 'pos_table', 'pos_idx',
                          'qkv', 'o', 'lse', 'y1', 's1', 'st1', 'pre', 'h', 's2', 'y2', 'st2', 'y2p', 'head_scale', 'wpack',
-                         'xpos_table', 'xpos_idx')]))
+                         'xpos_table', 'xpos_idx')] + [('tail_flags', ctypes.c_int32)]))
 EncoderLayerBwdArgs = _struct('EncoderLayerBwdArgs', 'sst_encoder_layer_bwd_args of include/sst_amd.h', (
     [('m', c_i64), ('n_windows', c_i64)] + [(k, ctypes.c_int32) for k in ('n_heads', 'act', 'max_tokens', 'impl')]
     + [('eps', ctypes.c_float), ('scale', ctypes.c_float)]
@@ -213,15 +213,17 @@ EncoderLayerBwdArgs = _struct('EncoderLayerBwdArgs', 'sst_encoder_layer_bwd_args
                          'w_in', 'w_out', 'w1', 'w2', 'n1w', 'n2w', 'tok', 'winoff', 'order',
                          'ds2', 'dpre', 'ds1', 'd_o', 'dqkv',
                          'dw_in', 'db_in', 'dwo', 'dbo', 'dw1', 'db1', 'dw2', 'db2', 'dn1w', 'dn1b', 'dn2w', 'dn2b',
-                         'workspace', 'head_scale', 'cos_r', 'dy1', 'wpack', 'xpos_table', 'xpos_idx')]))
+                         'workspace', 'head_scale', 'cos_r', 'dy1', 'wpack', 'xpos_table', 'xpos_idx')]
+    + [('tail_flags', ctypes.c_int32)]))
 
 
+TAIL_HANDOVER = 1      # SST_TAIL_HANDOVER of include/sst_amd.h
 EncoderTailFwdArgs = _struct('EncoderTailFwdArgs', 'sst_encoder_tail_fwd_args of include/sst_amd.h', (
-    [('m', c_i64), ('act', ctypes.c_int32), ('reserved', ctypes.c_int32), ('eps', ctypes.c_float), ('reserved_f', ctypes.c_float)]
+    [('m', c_i64), ('act', ctypes.c_int32), ('flags', ctypes.c_int32), ('eps', ctypes.c_float), ('reserved_f', ctypes.c_float)]
     + [(k, _P) for k in ('o', 'x', 'packed', 'b_out', 'b1', 'b2', 'n1w', 'n1b', 'n2w', 'n2b', 'pos_table', 'pos_idx',
                          's1', 'st1', 'y1', 'pre', 'h', 's2', 'st2', 'y2', 'y2p')]))
 EncoderTailBwdArgs = _struct('EncoderTailBwdArgs', 'sst_encoder_tail_bwd_args of include/sst_amd.h', (
-    [('m', c_i64), ('act', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+    [('m', c_i64), ('act', ctypes.c_int32), ('flags', ctypes.c_int32)]
     + [(k, _P) for k in ('dy2', 'dy2p', 's2', 'st2', 'pre', 's1', 'st1', 'packed', 'n1w', 'n2w',
                          'ds2', 'dpre', 'ds1', 'd_o', 'dn2w', 'dn2b', 'dn1w', 'dn1b', 'workspace')]))
 
@@ -272,6 +274,7 @@ _SIGNATURES = {
     'sst_encoder_layer_wpack_bytes': (c_i64, []),
     'sst_encoder_layer_fwd_f32x6': (c_i32, [c_ptr, c_ptr]),
     'sst_encoder_layer_bwd_f32x6': (c_i32, [c_ptr, c_ptr]),
+    'sst_encoder_tail_handover_rows': (c_i64, [c_i64]),
     'sst_encoder_tail_pack_bytes': (c_i64, []),
     'sst_encoder_tail_pack_f32x6': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sst_encoder_tail_pack_f32x6_many': (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_ptr]),

@@ -30,5 +30,15 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
   const float phi = 0.5f * (1.f + erf_as(x * 0.70710678118654752f, e));
   return fmaf(x * 0.3989422804014327f, e, phi);
 }
+// gelu_f(x) (returned) and gelu_grad_f(x) (grad) from ONE erf_as evaluation, each with the bits of its own function: both are
+// formed from the same s = 1 + erf by the operations those functions apply to it - (0.5 x) s and fma(x / sqrt(2 pi), e, 0.5 s).
+// The products are rounded on their own (__fmul_rn is never contracted), the one fused operation is spelled out, so the
+// combined expression leaves the compiler nothing to contract differently from the two separate ones.
+__device__ __forceinline__ float gelu_with_grad_f(float x, float& grad) {
+  float e;
+  const float s = 1.f + erf_as(x * 0.70710678118654752f, e);
+  grad = fmaf(__fmul_rn(x, 0.3989422804014327f), e, __fmul_rn(0.5f, s));
+  return __fmul_rn(__fmul_rn(0.5f, x), s);
+}
 
 }  // namespace

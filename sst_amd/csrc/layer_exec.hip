@@ -96,7 +96,7 @@ int sst_encoder_layer_fwd_f32x6(const sst_encoder_layer_fwd_args* a, void* strea
     if (rc) return rc;
   }
   sst_encoder_tail_fwd_args t;
-  t.m = m, t.act = a->act, t.reserved = 0, t.eps = a->eps, t.reserved_f = 0.f;
+  t.m = m, t.act = a->act, t.flags = a->tail_flags, t.eps = a->eps, t.reserved_f = 0.f;
   t.o = a->o, t.x = a->x, t.packed = a->wpack;
   t.b_out = a->b_out, t.b1 = a->b1, t.b2 = a->b2, t.n1w = a->n1w, t.n1b = a->n1b, t.n2w = a->n2w, t.n2b = a->n2b;
   t.pos_table = a->pos_table, t.pos_idx = a->pos_idx;
@@ -122,7 +122,7 @@ int sst_encoder_layer_bwd_f32x6(const sst_encoder_layer_bwd_args* a, void* strea
   // norm2' -> linear2' * act' -> linear1' + residual -> norm1' -> out-projection' in one kernel; d(gamma) | d(beta) of both
   // LayerNorms stay as per-workgroup partials for the reduction launch of the weight gradients below
   sst_encoder_tail_bwd_args t;
-  t.m = m, t.act = a->act, t.reserved = 0;
+  t.m = m, t.act = a->act, t.flags = a->tail_flags;
   t.dy2 = a->dy2, t.dy2p = a->dy2p, t.s2 = a->s2, t.st2 = a->st2, t.pre = a->pre, t.s1 = a->s1, t.st1 = a->st1;
   t.packed = a->wpack, t.n1w = a->n1w, t.n2w = a->n2w;
   t.ds2 = a->ds2, t.dpre = a->dpre, t.ds1 = a->ds1, t.d_o = a->d_o;

@@ -21,6 +21,24 @@
 // is cut into two k-halves (128 x 64, 55 KB each).  A workgroup (8 waves, 128 tokens) walks the 10 chunks with two LDS slots:
 // the fp32 weights of chunk i + 1 are requested from L2 before chunk i is multiplied, split and stored after it, one barrier per
 // chunk.  Weight traffic is L2 -> LDS only (0.5 MB per 128 tokens against 0.7 MB of HBM traffic for the same tokens).
+//
+// Two layouts of what the forward kernel leaves, and who reads what:
+//   row-major [m][width], through the wave's 2 KiB LDS block (store32 / load32_*): every tensor another kernel reads - y1, h
+//     (weight gradients), y2, y2p (the next layer), st1, st2, and the backward kernel's ds2, dpre, ds1 (weight gradients), d_o
+//     (attention backward).  With flags = 0 also s1, s2 and pre: the default of the C entry points.
+//   hand-over (flags & SST_TAIL_HANDOVER; store_ho / load_ho): s1, s2 and the feed-forward tensor have ONE reader, the backward
+//     kernel of this file.  They are written as they lie in the fragment registers -
+//     [row / 16][column block of 32][half][lane][4 floats], 1 KiB contiguous per wave instruction, no LDS block, no wait in front
+//     of the store - and read back with two 16-byte loads per block at the places the row-major requests stand (the chunk
+//     choreography, the barriers and the one-chunk-ahead request of the feed-forward tensor are the same in both modes).  The
+//     feed-forward tensor then holds act'(pre), not pre: the backward kernel uses pre for nothing else, and the forward kernel
+//     has erf and exp(-pre^2 / 2) at hand when it forms h (gelu_with_grad_f of csrc/gelu.h, bit for bit gelu_f and
+//     gelu_grad_f), so the backward chunk loop evaluates nothing.  16 of the 40 blocks each kernel moves per 16 tokens go this
+//     way.  Buffers hold sst_encoder_tail_handover_rows(m) rows: a tile for every wave of every workgroup.  The forward kernel
+//     WRITES the rows past m (with what its clamped loads gave them: the values of row m - 1); the backward kernel reads them
+//     and lets them contribute nothing, whatever they hold: a token never leaves its lane column, invalid tokens are masked out
+//     of the LayerNorm parameter gradients and are not stored.  Every other tensor has the same bits in both modes
+//     (tests/test_gpu_encoder_tail_handover.py).
 #include <math.h>
 #include <stdlib.h>
 #include "common.h"
@@ -261,6 +279,46 @@ __device__ __forceinline__ void load32_finish(const tile_io& t, const f32x4 (&w)
   v1 = *(const f32x4*)(t.scr + (t.frag_off0 ^ 16));
 }
 
+// ---- the hand-over layout: fragment registers <-> global memory with no LDS block -----------------------------------------------
+// s1, s2 and the feed-forward tensor are written by the forward kernel and read by the backward kernel of this file, by nobody
+// else: in hand-over mode they lie in memory as they lie in registers.  A tensor of width 32 * ncb is
+//   [tile = row / 16][column block of 32][half 0..1][lane 0..63][4 floats]
+// where lane (c, g) holds columns 8 g + 4 half .. + 3 of the block for token 16 tile + c (fragment register v0 = half 0, v1 =
+// half 1): a wave instruction moves 1 KiB contiguous, the pair a block's 2 KiB.  The tile index is the wave's
+// (workgroup * kWaves + wave): every wave of every launched workgroup has a tile, the buffer holds
+// sst_encoder_tail_handover_rows(m) rows (m rounded up to kRowsPerWg).
+__device__ __forceinline__ int64_t ho_tile(int wave) {   // wave-uniform: the block address stays in scalar registers
+  return (int64_t)blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(wave);
+}
+// the block's address as a scalar pair the accesses take beside the one lane-offset register (global_* v, v, s[..]): without the
+// two readfirstlane (free on a value that is scalar already) the compiler folds the lane offset into a 64-bit vector address
+// per tensor, two registers each in kernels that have none to spare
+typedef __attribute__((address_space(1))) unsigned char gbyte;
+__device__ __forceinline__ gbyte* ho_block(const float* base, int64_t tile, int ncb, int cb) {
+  const uint64_t b = (uint64_t)((const unsigned char*)base + (tile * ncb + cb) * (int64_t)kScr);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+  return (gbyte*)(((uint64_t)hi << 32) | lo);
+}
+// the lane's byte offset as a 32-bit value formed next to its use (the empty statement keeps it from being widened to 64 bits
+// once and for all above the chunk loop, which is the form the scalar-base access cannot take)
+__device__ __forceinline__ unsigned ho_lane_off(int lane) {
+  unsigned off = (unsigned)lane * 16u;
+  asm volatile("" : "+v"(off));
+  return off;
+}
+__device__ __forceinline__ void store_ho(float* base, int64_t tile, int ncb, int cb, int lane, const f32x4& v0, const f32x4& v1) {
+  gbyte* p = ho_block(base, tile, ncb, cb);
+  const unsigned off = ho_lane_off(lane);
+  __builtin_nontemporal_store(v0, (__attribute__((address_space(1))) f32x4*)(p + off));
+  __builtin_nontemporal_store(v1, (__attribute__((address_space(1))) f32x4*)(p + 1024 + off));
+}
+__device__ __forceinline__ void load_ho(const float* base, int64_t tile, int ncb, int cb, int lane, f32x4 (&w)[2]) {
+  const gbyte* p = ho_block(base, tile, ncb, cb);
+  const unsigned off = ho_lane_off(lane);
+  w[0] = *(const __attribute__((address_space(1))) f32x4*)(p + off);
+  w[1] = *(const __attribute__((address_space(1))) f32x4*)(p + 1024 + off);
+}
+
 // ---- the three products on a wave's 16 tokens -------------------------------------------------------------------------------
 // out-projection k-half (two k-steps, 8 output tiles): acc[T] += W(slot)[T] x(ks), x split on the way (smallest products first)
 template <int HALF>
@@ -399,7 +457,11 @@ struct tail_fwd_params {
   float* y2p;
 };
 
-template <int ACT>   // 1 = GELU(erf), 2 = ReLU
+// HO (hand-over mode): s1, s2 and the feed-forward tensor leave in the hand-over layout, straight from the fragment registers,
+// and the feed-forward tensor holds act'(pre) instead of pre - the one thing the backward kernel wants from it (GELU: from the
+// erf and the exponential that h needs anyway; ReLU: 1 / 0 by pre > 0).  Rows past m of the last workgroup ARE written: they
+// carry what the clamped loads gave them (row m - 1), the buffers are padded for them.
+template <int ACT, bool HO>   // ACT: 1 = GELU(erf), 2 = ReLU
 __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_params P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   float* par = (float*)(lds + kArea);   // b_o | g1 | be1 | b2 | g2 | be2 | b1[256]
@@ -408,6 +470,7 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
   const bool valid = r0 + c < P.m;
   const int64_t row = valid ? r0 + c : P.m - 1;
   const tile_io io = make_tile_io(lds + kArea + kParF * 4 + wave * kScr, lane, r0, P.m);
+  const int64_t tile = HO ? ho_tile(wave) : 0;
   const unsigned char* packed = P.packed;
   unsigned char* const part2 = lds + kPart1;
   dma_pieces<kWaves>(packed, lds, 3 * kIA / 1024, wave, lane);   // out-projection half 0
@@ -462,7 +525,12 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
       const int n0 = 32 * s + 8 * g;
       v[s][0] = acc[2 * s] + *(const f32x4*)(par + n0) + xr[s][0];
       v[s][1] = acc[2 * s + 1] + *(const f32x4*)(par + n0 + 4) + xr[s][1];
-      if (P.s1 != nullptr) store32<true>(io, P.s1, kC, 32 * s, v[s][0], v[s][1]);
+      if (P.s1 != nullptr) {
+        if (HO)
+          store_ho(P.s1, tile, 4, s, lane, v[s][0], v[s][1]);
+        else
+          store32<true>(io, P.s1, kC, 32 * s, v[s][0], v[s][1]);
+      }
     }
     float mean, rstd;
     ln_stats(v, P.eps, mean, rstd);
@@ -479,11 +547,14 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
     for (int T = 0; T < 8; ++T) acc[T] = z4;
   }
   barrier_drain();   // chunk 0's images have landed
-  f32x4 sp0 = z4, sp1 = z4, sh0 = z4, sh1 = z4;   // pre | h of the previous chunk, stored one phase later
+  f32x4 sp0 = z4, sp1 = z4, sh0 = z4, sh1 = z4;   // pre (HO: act'(pre)) | h of the previous chunk, stored one phase later
 #pragma unroll 1
   for (int j = 0; j < kNF; ++j) {
     if (j > 0) {   // behind the barrier that needed no store to be finished; acknowledged by the next drain, a whole phase away
-      store32<true>(io, P.pre, kFF, kHC * (j - 1), sp0, sp1);
+      if (HO)
+        store_ho(P.pre, tile, kNF, j - 1, lane, sp0, sp1);
+      else
+        store32<true>(io, P.pre, kFF, kHC * (j - 1), sp0, sp1);
       store32<true>(io, P.h, kFF, kHC * (j - 1), sh0, sh1);
     }
     f32x4 p0, p1;
@@ -494,8 +565,20 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
     f32x4 h0, h1;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      h0[r] = ACT == 1 ? gelu_f(p0[r]) : fmaxf(p0[r], 0.f);
-      h1[r] = ACT == 1 ? gelu_f(p1[r]) : fmaxf(p1[r], 0.f);
+      if (!HO) {
+        h0[r] = ACT == 1 ? gelu_f(p0[r]) : fmaxf(p0[r], 0.f);
+        h1[r] = ACT == 1 ? gelu_f(p1[r]) : fmaxf(p1[r], 0.f);
+      } else if (ACT == 1) {   // p <- gelu'(p) on the way
+        float d0, d1;
+        h0[r] = gelu_with_grad_f(p0[r], d0);
+        h1[r] = gelu_with_grad_f(p1[r], d1);
+        p0[r] = d0, p1[r] = d1;
+      } else {
+        h0[r] = fmaxf(p0[r], 0.f);
+        h1[r] = fmaxf(p1[r], 0.f);
+        p0[r] = p0[r] > 0.f ? 1.f : 0.f;
+        p1[r] = p1[r] > 0.f ? 1.f : 0.f;
+      }
     }
     const img3 hs = split8(h0, h1);
     barrier_drain();   // part 1 is free; this chunk's part 2 has landed; the previous chunk's stores are acknowledged
@@ -505,7 +588,10 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
     barrier_drain();   // part 2 is free, the next chunk's part 1 has landed (nothing else is in flight)
     if (j + 1 < kNF) dma_pieces<kWaves>(packed + (size_t)(j + 3) * kSlot + kPart1, part2, kPart2 / 1024, wave, lane);
   }
-  store32<true>(io, P.pre, kFF, kHC * (kNF - 1), sp0, sp1);
+  if (HO)
+    store_ho(P.pre, tile, kNF, kNF - 1, lane, sp0, sp1);
+  else
+    store32<true>(io, P.pre, kFF, kHC * (kNF - 1), sp0, sp1);
   store32<true>(io, P.h, kFF, kHC * (kNF - 1), sh0, sh1);
   // s2 = y1 + linear2 + b2; y2 = LN2(s2) (; y2p = y2 + positional rows of the next layer)
   f32x4 v[4][2];
@@ -516,7 +602,12 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_fwd_x6_k(const tail_fwd_
     join8(yi[s], ya, yb);
     v[s][0] = acc[2 * s] + *(const f32x4*)(par + 3 * kC + n0) + ya;
     v[s][1] = acc[2 * s + 1] + *(const f32x4*)(par + 3 * kC + n0 + 4) + yb;
-    if (P.s2 != nullptr) store32<true>(io, P.s2, kC, 32 * s, v[s][0], v[s][1]);
+    if (P.s2 != nullptr) {
+      if (HO)
+        store_ho(P.s2, tile, 4, s, lane, v[s][0], v[s][1]);
+      else
+        store32<true>(io, P.s2, kC, 32 * s, v[s][0], v[s][1]);
+    }
   }
   float mean, rstd;
   ln_stats(v, P.eps, mean, rstd);
@@ -582,7 +673,11 @@ __device__ __forceinline__ void ln_bwd(f32x4 (&d)[4][2], f32x4 (&sv)[4][2], cons
       for (int r = 0; r < 4; ++r) d[s][h][r] = st.y * (d[s][h][r] - mg - sv[s][h][r] * mgx);
 }
 
-template <int ACT>
+// HO (hand-over mode): s2, s1 and the feed-forward tensor arrive in the hand-over layout, two 16-byte loads per block straight
+// into the fragment registers, requested where the row-major loads are; P.pre holds act'(pre), nothing is evaluated.  Rows past
+// m contribute nothing whatever they hold: they stay in their own lanes (a token is a lane column of every product), their
+// LayerNorm parameter-gradient terms are masked and their rows are not stored, as in the row-major mode.
+template <int ACT, bool HO>
 __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_params P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   float* par = (float*)(lds + kArea);        // gamma2 | gamma1
@@ -592,6 +687,20 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_
   const bool valid = r0 + c < P.m;
   const int64_t row = valid ? r0 + c : P.m - 1;
   const tile_io io = make_tile_io(lds + kArea + 2 * kC * 4 + kWaves * 2 * kC * 4 + wave * kScr, lane, r0, P.m);
+  const int64_t tile = HO ? ho_tile(wave) : 0;
+  // a 32-column block of a tensor only this kernel reads: requested (row side / hand-over layout) ... and taken into the fragment
+  auto saved_issue = [&](const float* base, int ncb, int cb, f32x4 (&w)[2]) __attribute__((always_inline)) {
+    if (HO)
+      load_ho(base, tile, ncb, cb, lane, w);
+    else
+      load32_issue(io, base, 32 * ncb, 32 * cb, w);
+  };
+  auto saved_finish = [&](const f32x4 (&w)[2], f32x4& v0, f32x4& v1) __attribute__((always_inline)) {
+    if (HO)
+      v0 = w[0], v1 = w[1];
+    else
+      load32_finish(io, w, v0, v1);
+  };
   const unsigned char* packed = P.packed;
   unsigned char* const part2 = lds + kPart1;
   dma_pieces<kWaves>(packed, lds, kSlot / 1024, wave, lane);   // feed-forward chunk 0, both parts: lands behind the first LayerNorm backward
@@ -610,11 +719,11 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_
       }
     }
 #pragma unroll
-    for (int s = 0; s < 4; ++s) load32_issue(io, P.s2, kC, 32 * s, we[s]);
+    for (int s = 0; s < 4; ++s) saved_issue(P.s2, 4, s, we[s]);
 #pragma unroll
     for (int s = 0; s < 4; ++s) load32_finish(io, wd[s], d[s][0], d[s][1]);
 #pragma unroll
-    for (int s = 0; s < 4; ++s) load32_finish(io, we[s], sv[s][0], sv[s][1]);
+    for (int s = 0; s < 4; ++s) saved_finish(we[s], sv[s][0], sv[s][1]);
   }
   const float2 st2 = ((const float2*)P.st2)[row];
   for (int i = threadIdx.x; i < kC; i += kNTH) {
@@ -638,8 +747,8 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_
 #pragma unroll
   for (int T = 0; T < 8; ++T) acc[T] = z4;
   f32x4 xs1[4][2];   // ds1 (fp32): B operand of the out-projection's data gradient
-  f32x4 pq[2];       // the pre-activation of the running chunk (row side), requested one chunk ahead
-  load32_issue(io, P.pre, kFF, 0, pq);
+  f32x4 pq[2];       // the pre-activation (HO: its act') of the running chunk, requested one chunk ahead
+  saved_issue(P.pre, kNF, 0, pq);
 
   // chunk choreography as in the forward kernel: one slot, its two parts alternate between "being read" and "being filled"
   // feed-forward chunk j: dpre_j = (ds2 W2[:, 32 j ..]) act'(pre_j), d(y1) += dpre_j W1[32 j .., :]
@@ -650,8 +759,8 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_
     mma_first(lds, lane_off1, di, p0, p1);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      p0[r] *= ACT == 1 ? gelu_grad_f(q0[r]) : (q0[r] > 0.f ? 1.f : 0.f);
-      p1[r] *= ACT == 1 ? gelu_grad_f(q1[r]) : (q1[r] > 0.f ? 1.f : 0.f);
+      p0[r] *= HO ? q0[r] : ACT == 1 ? gelu_grad_f(q0[r]) : (q0[r] > 0.f ? 1.f : 0.f);
+      p1[r] *= HO ? q1[r] : ACT == 1 ? gelu_grad_f(q1[r]) : (q1[r] > 0.f ? 1.f : 0.f);
     }
     const img3 hs = split8(p0, p1);
     barrier_drain();   // part 1 is free (and this chunk's part 2 has landed)
@@ -675,21 +784,21 @@ __global__ __launch_bounds__(kNTH, 2) void encoder_tail_bwd_x6_k(const tail_bwd_
 #pragma unroll 1
   for (int j = 0; j < kNF - 1; ++j) {
     f32x4 q0, q1;
-    load32_finish(io, pq, q0, q1);
-    load32_issue(io, P.pre, kFF, kHC * (j + 1), pq);   // the next chunk's pre-activation
+    saved_finish(pq, q0, q1);
+    saved_issue(P.pre, kNF, j + 1, pq);   // the next chunk's pre-activation
     ffn_chunk(j, q0, q1);
   }
   {
     f32x4 q0, q1;
-    load32_finish(io, pq, q0, q1);
+    saved_finish(pq, q0, q1);
     ffn_chunk(kNF - 1, q0, q1);
     store32<SST_NT_BWD>(io, P.dpre, kFF, kHC * (kNF - 1), sd0, sd1);
     {   // norm1's input (requested here: a tile of it held across the chunk spills)
       f32x4 ws[4][2];
 #pragma unroll
-      for (int s = 0; s < 4; ++s) load32_issue(io, P.s1, kC, 32 * s, ws[s]);
+      for (int s = 0; s < 4; ++s) saved_issue(P.s1, 4, s, ws[s]);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) load32_finish(io, ws[s], xs1[s][0], xs1[s][1]);
+      for (int s = 0; s < 4; ++s) saved_finish(ws[s], xs1[s][0], xs1[s][1]);
     }
     // d(y1) = ds2 + dpre W1; norm1 backward -> ds1 (= d(x) of the residual, = d(out-projection output))
     f32x4 dd[4][2];
@@ -740,13 +849,21 @@ int configure(K kernel, int lds_bytes, unsigned long long* mask) {
   return SST_OK;
 }
 
+template <typename K, typename PARAMS>
+int launch_tail(K kernel, int lds_bytes, unsigned long long* mask, int64_t rows, hipStream_t st, const PARAMS& P) {
+  const int rc = configure(kernel, lds_bytes, mask);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(kNTH), lds_bytes, st, P);
+  return SST_OK;
+}
+
 }  // namespace
 
 // the backward kernel without a finishing launch for the LayerNorm parameter gradients: their per-workgroup partials stay in
 // the workspace as [rows][256] (norm2's first, norm1's `rows` rows later) for the caller's reduction launch (csrc/layer_exec.hip)
 int sst_internal_encoder_tail_bwd_f32x6(const sst_encoder_tail_bwd_args* a, float** part2, float** part1, int* partial_rows,
                                         void* stream) {
-  if (!a || a->m <= 0 || (a->act != 1 && a->act != 2)) return SST_ERR_ARG;
+  if (!a || a->m <= 0 || (a->act != 1 && a->act != 2) || (a->flags & ~SST_TAIL_HANDOVER)) return SST_ERR_ARG;
   const void* need[] = {a->dy2, a->s2, a->st2, a->n2w, a->pre, a->s1, a->st1, a->n1w, a->packed,
                         a->ds2, a->dpre, a->ds1, a->d_o, a->workspace};
   for (const void* p : need)
@@ -761,16 +878,15 @@ int sst_internal_encoder_tail_bwd_f32x6(const sst_encoder_tail_bwd_args* a, floa
   P.part2 = (float*)a->workspace;
   P.part1 = P.part2 + rows * 2 * kC;
   hipStream_t st = (hipStream_t)stream;
-  static unsigned long long cfg1 = 0, cfg2 = 0;
-  if (a->act == 1) {
-    const int rc = configure(encoder_tail_bwd_x6_k<1>, kLdsBwd, &cfg1);
-    if (rc) return rc;
-    hipLaunchKernelGGL(encoder_tail_bwd_x6_k<1>, dim3((unsigned)rows), dim3(kNTH), kLdsBwd, st, P);
-  } else {
-    const int rc = configure(encoder_tail_bwd_x6_k<2>, kLdsBwd, &cfg2);
-    if (rc) return rc;
-    hipLaunchKernelGGL(encoder_tail_bwd_x6_k<2>, dim3((unsigned)rows), dim3(kNTH), kLdsBwd, st, P);
-  }
+  static unsigned long long cfg[4] = {0, 0, 0, 0};
+  int rc;
+  if (a->flags & SST_TAIL_HANDOVER)
+    rc = a->act == 1 ? launch_tail(encoder_tail_bwd_x6_k<1, true>, kLdsBwd, &cfg[0], rows, st, P)
+                     : launch_tail(encoder_tail_bwd_x6_k<2, true>, kLdsBwd, &cfg[1], rows, st, P);
+  else
+    rc = a->act == 1 ? launch_tail(encoder_tail_bwd_x6_k<1, false>, kLdsBwd, &cfg[2], rows, st, P)
+                     : launch_tail(encoder_tail_bwd_x6_k<2, false>, kLdsBwd, &cfg[3], rows, st, P);
+  if (rc) return rc;
   SST_LAUNCH_CHECK();
   *part2 = P.part2, *part1 = P.part1, *partial_rows = (int)rows;
   return SST_OK;
@@ -831,13 +947,19 @@ int sst_encoder_tail_pack_f32x6(const float* d_w_out, const float* d_w1, const f
   return sst_encoder_tail_pack_f32x6_many(&d_w_out, &d_w1, &d_w2, &d_packed, 1, stream);
 }
 
+// rows of a hand-over buffer (s1, s2: x 128 floats, the feed-forward tensor: x 256): a 16-row tile for every wave of every workgroup
+int64_t sst_encoder_tail_handover_rows(int64_t m) {
+  if (m < 0) return SST_ERR_ARG;
+  return sst_div_up(m, (int64_t)kRowsPerWg) * kRowsPerWg;
+}
+
 int64_t sst_encoder_tail_bwd_workspace_bytes(int64_t m) {
   if (m < 0) return SST_ERR_ARG;
   return sst_align_up(2 * sst_div_up(m > 0 ? m : 1, (int64_t)kRowsPerWg) * 2 * kC * (int64_t)sizeof(float), 256);
 }
 
 int sst_encoder_tail_fwd_f32x6(const sst_encoder_tail_fwd_args* a, void* stream) {
-  if (!a || a->m < 0 || (a->act != 1 && a->act != 2)) return SST_ERR_ARG;
+  if (!a || a->m < 0 || (a->act != 1 && a->act != 2) || (a->flags & ~SST_TAIL_HANDOVER)) return SST_ERR_ARG;
   if (a->m == 0) return SST_OK;
   const void* need[] = {a->o, a->x, a->packed, a->n1w, a->n1b, a->n2w, a->n2b, a->st1, a->y1, a->pre, a->h, a->st2, a->y2};
   for (const void* p : need)
@@ -854,16 +976,15 @@ int sst_encoder_tail_fwd_f32x6(const sst_encoder_tail_fwd_args* a, void* stream)
   const int64_t rows = sst_div_up(a->m, (int64_t)kRowsPerWg);
   if (rows > 0x7fffffff) return SST_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  static unsigned long long cfg1 = 0, cfg2 = 0;
-  if (a->act == 1) {
-    const int rc = configure(encoder_tail_fwd_x6_k<1>, kLdsFwd, &cfg1);
-    if (rc) return rc;
-    hipLaunchKernelGGL(encoder_tail_fwd_x6_k<1>, dim3((unsigned)rows), dim3(kNTH), kLdsFwd, st, P);
-  } else {
-    const int rc = configure(encoder_tail_fwd_x6_k<2>, kLdsFwd, &cfg2);
-    if (rc) return rc;
-    hipLaunchKernelGGL(encoder_tail_fwd_x6_k<2>, dim3((unsigned)rows), dim3(kNTH), kLdsFwd, st, P);
-  }
+  static unsigned long long cfg[4] = {0, 0, 0, 0};
+  int rc;
+  if (a->flags & SST_TAIL_HANDOVER)
+    rc = a->act == 1 ? launch_tail(encoder_tail_fwd_x6_k<1, true>, kLdsFwd, &cfg[0], rows, st, P)
+                     : launch_tail(encoder_tail_fwd_x6_k<2, true>, kLdsFwd, &cfg[1], rows, st, P);
+  else
+    rc = a->act == 1 ? launch_tail(encoder_tail_fwd_x6_k<1, false>, kLdsFwd, &cfg[2], rows, st, P)
+                     : launch_tail(encoder_tail_fwd_x6_k<2, false>, kLdsFwd, &cfg[3], rows, st, P);
+  if (rc) return rc;
   SST_LAUNCH_CHECK();
   return SST_OK;
 }

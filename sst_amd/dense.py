@@ -468,17 +468,39 @@ def encoder_tail_pack(w_out, w1, w2, out=None):
     return out
 
 
-def encoder_tail_fwd(o, x, packed, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, save=True, pos=None, out=None):
+def handover_rows(m):
+    """rows of a hand-over buffer for m tokens (sst_encoder_tail_handover_rows: m rounded up to a workgroup's rows)"""
+    rows = int(_lib.load().sst_encoder_tail_handover_rows(m))
+    if rows < 0:
+        _lib.check(rows, 'sst_encoder_tail_handover_rows')
+    return rows
+
+
+def handover_to_rows(buf, m):
+    """a hand-over buffer of the tail kernels ([rows, cols] as allocated, rows a multiple of 16, cols of 32) as the row-major
+    [m, cols] tensor it stands for.  The kernels' layout (csrc/layer_tail_x6.hip) is
+    [tile of 16 rows][block of 32 columns][half 0..1][lane = 16 g + c][4 floats]: row 16 tile + c, column 32 block + 8 g + 4 half + e.
+    For tests and debugging only: the backward kernel reads the buffer as it lies."""
+    rows, cols = buf.shape
+    assert rows % 16 == 0 and cols % 32 == 0 and 0 <= m <= rows
+    v = buf.reshape(rows // 16, cols // 32, 2, 4, 16, 4)      # tile, block, half, g, c, e
+    return v.permute(0, 4, 1, 3, 2, 5).reshape(rows, cols)[:m]
+
+
+def encoder_tail_fwd(o, x, packed, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, save=True, pos=None, out=None, handover=False):
     """y1 = LN1(x + o W_o^T + b_o); pre = y1 W_1^T + b_1; h = act(pre); s2 = y1 + h W_2^T + b_2; y2 = LN2(s2) as ONE kernel
     (sst_basic_block_v2.py:113-118); packed = encoder_tail_pack(W_o, W_1, W_2).  -> dict(s1 (None unless save), st1, y1, pre,
-    h, s2, st2, y2, y2p (pos = (table, index))); ``out``: optional dict of preallocated tensors by the same names."""
+    h, s2, st2, y2, y2p (pos = (table, index))); ``out``: optional dict of preallocated tensors by the same names.
+    handover: s1, pre, s2 are hand-over buffers ([handover_rows(m), cols], tile-blocked, ``pre`` holding act'(pre)) that only
+    encoder_tail_bwd(..., handover=True) reads - what a caller wants who keeps them for nothing but that call."""
     m = x.size(0)
     dev = x.device
     out = dict(out) if out else {}
+    rows_ho = handover_rows(m) if handover else m
 
     def e(name, cols):
         if name not in out or out[name] is None:
-            out[name] = torch.empty((m, cols), dtype=torch.float32, device=dev)
+            out[name] = torch.empty((rows_ho if name in ('s1', 'pre', 's2') else m, cols), dtype=torch.float32, device=dev)
         return out[name]
     s1 = e('s1', 128) if save else None
     out['s1'] = s1
@@ -487,7 +509,8 @@ def encoder_tail_fwd(o, x, packed, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, 
     out['y2p'] = y2p
     P = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     args = _lib.EncoderTailFwdArgs(
-        m, 1 if act == 'gelu' else 2, 0, float(eps), 0.0, P(o), P(x), P(packed), P(b_out), P(b1), P(b2), P(n1w), P(n1b),
+        m, 1 if act == 'gelu' else 2, _lib.TAIL_HANDOVER if handover else 0, float(eps), 0.0, P(o), P(x), P(packed), P(b_out),
+        P(b1), P(b2), P(n1w), P(n1b),
         P(n2w), P(n2b), P(pos[0]) if pos is not None else None, P(pos[1]) if pos is not None else None,
         P(s1), P(st1), P(y1), P(pre), P(h), P(s2), P(st2), P(y2), P(y2p))
     import ctypes
@@ -495,11 +518,16 @@ def encoder_tail_fwd(o, x, packed, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, 
     return out
 
 
-def encoder_tail_bwd(dy2, dy2p, s2, st2, pre, s1, st1, packed, n1w, n2w, act, out=None):
+def encoder_tail_bwd(dy2, dy2p, s2, st2, pre, s1, st1, packed, n1w, n2w, act, out=None, handover=False):
     """the backward of encoder_tail_fwd up to the attention output: -> (ds2, dpre, ds1, d_o, dn [4, 128] = dn2w | dn2b | dn1w | dn1b);
     the weight gradients of the three linears are left to the caller (ds2 with h, dpre with y1, ds1 with o).
-    ``out``: optional dict of preallocated contiguous tensors by the names ds2, dpre, ds1, d_o, dn and ws (the workspace, uint8)."""
+    ``out``: optional dict of preallocated contiguous tensors by the names ds2, dpre, ds1, d_o, dn and ws (the workspace, uint8).
+    handover: s2, pre, s1 are the hand-over buffers of encoder_tail_fwd(..., handover=True)."""
     m = dy2.size(0)
+    if handover:
+        rows_ho = handover_rows(m)
+        if not all(t.is_contiguous() and t.numel() == rows_ho * c for t, c in ((s1, 128), (pre, 256), (s2, 128))):
+            raise RuntimeError('sst_amd: encoder_tail_bwd(handover=True) takes the buffers encoder_tail_fwd(handover=True) wrote')
     dev = dy2.device
     out = out or {}
 
@@ -511,7 +539,7 @@ def encoder_tail_bwd(dy2, dy2p, s2, st2, pre, s1, st1, packed, n1w, n2w, act, ou
     ws = out['ws'] if 'ws' in out else _lib.workspace(lib.sst_encoder_tail_bwd_workspace_bytes(m), dev)
     P = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     d0 = dn.data_ptr()
-    args = _lib.EncoderTailBwdArgs(m, 1 if act == 'gelu' else 2, 0, P(dy2), P(dy2p), P(s2), P(st2), P(pre), P(s1), P(st1), P(packed),
+    args = _lib.EncoderTailBwdArgs(m, 1 if act == 'gelu' else 2, _lib.TAIL_HANDOVER if handover else 0, P(dy2), P(dy2p), P(s2), P(st2), P(pre), P(s1), P(st1), P(packed),
                                    P(n1w), P(n2w), P(ds2), P(dpre), P(ds1), P(d_o), d0, d0 + 512, d0 + 1024, d0 + 1536, P(ws))
     import ctypes
     _lib.check(lib.sst_encoder_tail_bwd_f32x6(ctypes.byref(args), _lib.stream_ptr()), 'sst_encoder_tail_bwd_f32x6')

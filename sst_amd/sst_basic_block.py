@@ -239,11 +239,18 @@ _SLAB = (('qkv', 384), ('o', 128), ('lse', 8), ('s1', 128), ('st1', 2), ('y1', 1
          ('st2', 2))
 
 
+# s1, pre, s2 are the tail kernels' private hand-over (csrc/layer_tail_x6.hip, SST_TAIL_HANDOVER): tile-blocked buffers of
+# handover_rows(m) rows that the backward tail alone reads; every other piece is a row-major [m, cols] tensor
+_SLAB_HANDOVER = ('s1', 'pre', 's2')
+
+
 def _slab_offsets(m):
+    from .dense import handover_rows
+    rows_ho = handover_rows(m)
     off, out = 0, {}
     for name, cols in _SLAB:
         out[name] = off
-        off += (m * cols * 4 + 255) // 256 * 256
+        off += ((rows_ho if name in _SLAB_HANDOVER else m) * cols * 4 + 255) // 256 * 256
     return out, off
 
 
@@ -276,7 +283,7 @@ def _layer_exec_fwd(x, xp, plan, nhead, impl, act, params, eps, scale, pos_next,
         P(pos_next[0]) if pos_next is not None else None, P(pos_next[1]) if pos_next is not None else None,
         S('qkv'), S('o'), S('lse'), S('y1'), S('s1') if need_bwd else None, S('st1'), S('pre'), S('h'), S('s2'), P(y2), S('st2'),
         P(y2p), P(head_scale), P(wpack), P(pos_spec[0]) if pos_spec is not None else None,
-        P(pos_spec[1]) if pos_spec is not None else None)
+        P(pos_spec[1]) if pos_spec is not None else None, _lib.TAIL_HANDOVER)
     rc = K._bracket('sra_fwd', plan.n_tokens, lambda: lib.sst_encoder_layer_fwd_f32x6(ctypes.byref(args), _lib.stream_ptr()))
     if rc == _lib.SST_ERR_UNSUPPORTED:     # a layout one of the entry points does not take: the Python sequence has the retries
         return None
@@ -328,7 +335,7 @@ def _layer_exec_bwd(ctx, dy2, dy2p, saved):
         p_ds2, p_dpre, P(ds1), p_do, p_dqkv,
         P(dw_in), P(db_in), P(dwo), P(dbo), P(dw1), P(db1), P(dw2), P(db2), dnp, dnp + 512, dnp + 1024, dnp + 1536, P(ws),
         P(head_scale), P(cos_r), None, P(wpack), P(pos_spec[0]) if pos_spec is not None else None,
-        P(pos_spec[1]) if pos_spec is not None else None)
+        P(pos_spec[1]) if pos_spec is not None else None, _lib.TAIL_HANDOVER)
     rc = K._bracket('sra_bwd', plan.n_tokens, lambda: lib.sst_encoder_layer_bwd_f32x6(ctypes.byref(args), _lib.stream_ptr()))
     _lib.check(rc, 'sst_encoder_layer_bwd_f32x6')
     d_scale = K.head_scale_grad(cos_r, head_scale) if head_scale is not None else None
@@ -472,7 +479,9 @@ class FusedEncoderLayerFn(torch.autograd.Function):
             # everything behind the attention core as ONE kernel (csrc/layer_tail_x6.hip), as csrc/layer_exec.hip issues it
             if wpack is None:
                 wpack = encoder_tail_pack(w_out, w1, w2)
-            t = encoder_tail_fwd(o, x, wpack, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, save=need_bwd, pos=pos_next)
+            # s1, pre, s2 are kept for encoder_tail_bwd alone: the kernels' hand-over layout (pre = act'(pre))
+            t = encoder_tail_fwd(o, x, wpack, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, save=need_bwd, pos=pos_next,
+                                 handover=True)
             s1, st1, y1, pre, h, s2, st2, y2, y2p = (t[k] for k in ('s1', 'st1', 'y1', 'pre', 'h', 's2', 'st2', 'y2', 'y2p'))
             ctx.tail = True
         else:
@@ -569,7 +578,7 @@ class FusedEncoderLayerFn(torch.autograd.Function):
         if ctx.tail:
             # norm2' -> linear2' * act' -> linear1' + residual -> norm1' -> out-projection' as ONE kernel (csrc/layer_tail_x6.hip)
             ds2, dpre, ds1, do, dn = encoder_tail_bwd(dy2.contiguous(), dy2p.contiguous() if (ctx.two and dy2p is not None) else None,
-                                                      s2, st2, pre, s1, st1, wpack, n1w, n2w, ctx.act)
+                                                      s2, st2, pre, s1, st1, wpack, n1w, n2w, ctx.act, handover=True)
             ds2_for_w2 = ds2
             dn2w, dn2b, dn1w, dn1b = dn[0], dn[1], dn[2], dn[3]
         else:

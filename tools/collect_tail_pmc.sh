@@ -16,4 +16,4 @@ for i in 1 2 3; do
   f=$(ls /tmp/pm$i/*counter_collection.csv 2>/dev/null | head -1)
   if [ -n "$f" ]; then grep -E "Kernel_Name|encoder_tail|tall_linear_f32x6_k<128, 128, 1>" "$f" > "$R/$OUT/sq_set$i.csv"; fi
 done
-python "$R/tools/pmc_summary.py" 'encoder_tail_(fwd|bwd)_x6_k<[0-9]+>|tall_linear_f32x6_k<128, 128, 1>' "$R/$OUT"/sq_set*.csv | tee "$R/$OUT/summary.txt"
+python "$R/tools/pmc_summary.py" 'encoder_tail_(fwd|bwd)_x6_k<[0-9]+, (true|false)>|tall_linear_f32x6_k<128, 128, 1>' "$R/$OUT"/sq_set*.csv | tee "$R/$OUT/summary.txt"

@@ -98,8 +98,12 @@ def main():
         out = D.add_ln_fwd(s2, None, n2w, n2b, eps, pos=pos)
         keep['u'] = (y1, s1, st1, h, pre, s2, out)
 
-    t_f, t_u = timed(fused_fwd), timed(unfused_fwd)
-    out = keep['out']
+    def handover_fwd():     # s1, pre, s2 in the kernels' private layout (what the fused layer path keeps)
+        keep['ho'] = D.encoder_tail_fwd(o, x, packed, b_out, b1, b2, n1w, n1b, n2w, n2b, eps, act, save=True, pos=pos,
+                                        out=keep.get('ho'), handover=True)
+
+    t_f, t_u, t_h = timed(fused_fwd), timed(unfused_fwd), timed(handover_fwd)
+    out, ho = keep['out'], keep['ho']
     dy2 = r(m, 128)
 
     def fused_bwd():
@@ -113,12 +117,16 @@ def main():
         d_o = D.lds_linear(ds1, w_out, None, trans_w=True)
         keep['ub'] = (ds2, dpre, dy1, ds1, d_o)
 
-    tb_f, tb_u = timed(fused_bwd), timed(unfused_bwd)
+    def handover_bwd():
+        keep['hb'] = D.encoder_tail_bwd(dy2, None, ho['s2'], ho['st2'], ho['pre'], ho['s1'], ho['st1'], packed, n1w, n2w, act,
+                                        handover=True)
+
+    tb_f, tb_u, tb_h = timed(fused_bwd), timed(unfused_bwd), timed(handover_bwd)
     unit = m * 512 / 1e9   # GB of one [M, 128] fp32 tensor
     print(json.dumps({
         'm': m, 'pack_us': round(t_pack, 1),
-        'fwd_us': {'one_kernel': round(t_f, 1), 'launch_per_product': round(t_u, 1)},
-        'bwd_us': {'one_kernel': round(tb_f, 1), 'launch_per_product': round(tb_u, 1)},
+        'fwd_us': {'one_kernel': round(t_f, 1), 'one_kernel_handover': round(t_h, 1), 'launch_per_product': round(t_u, 1)},
+        'bwd_us': {'one_kernel': round(tb_f, 1), 'one_kernel_handover': round(tb_h, 1), 'launch_per_product': round(tb_u, 1)},
         'fwd_algorithmic_GBps': round(11 * unit / (t_f * 1e-6), 0),      # reads o, x; writes s1, y1, pre, h, s2, y2, y2p
         'bwd_algorithmic_GBps': round(10 * unit / (tb_f * 1e-6), 0),     # reads dy2, s2, pre, s1; writes ds2, dpre, ds1, d_o
     }))
